@@ -14,7 +14,7 @@ Since round 6 the HEADLINE is the proof itself: a step of the timed region = ONE
 between barriers, the last one accepted by a verifier after the timed region; metric = constraints/sec = n / (time of one proof).  The op mix
 above, on its own seeded inputs, is measured first as `op_mix` (the headline of rounds 1-5; `--headline op-mix` times only that).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 24] [--curve bn254]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 24] [--curve bn254] [--dump-outputs DIR]
 
 N == 1: everything on one GPU.  Default n = 2^24, the size BASELINE.json's metric is quoted on (it fits one
         MI355X: the 8n = 2^27 transforms ping-pong two 4 GiB buffers); `--log-n 20` is configs[1].

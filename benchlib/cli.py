@@ -73,6 +73,11 @@ def parse():
                          "main thread (rank 0 of 8 simulated: 101.6 -> 96.2 ms per step)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: validate the arguments for this --gpus (divisibility of r and n, class count, buffer sizes per rank) and print the plan")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float64, a 64-bit limb as "
+                         "its two 32-bit halves; long vectors as a fixed seeded sample; 64 MB at most; benchlib/dump.py): the proof's commitments, "
+                         "evaluations and openings for the proof headline, the step's commitment and transform results for --headline op-mix.  "
+                         "Rank 0 writes; the line gets a `dump_outputs` field")
     ap.add_argument("--multi-path", action="store_true",
                     help="diagnostic: run the N > 1 code path (communicators, collectives, class scheme) on a world of ONE rank")
     ap.add_argument("--transport", default="rccl", choices=["rccl", "torch"],

@@ -26,10 +26,12 @@ def timed_steps(b, guard, steps=None, warmup=None):
     w.profile_enable(True)
     b.phase["ntt"] = b.phase["msm"] = 0.0
     t0 = time.perf_counter()
+    last = None
     for _ in range(steps):
-        b.step()
+        last = b.step()
     b.full_sync()
     dt = time.perf_counter() - t0
+    b.last_step_out = last                     # the last step's commitment (--dump-outputs)
     if b.overlap or b.overlap_multi:
         # under overlap the second figure is a WAIT, not a phase — it is named for what it is
         phases_ms = {"transforms_with_commitments_beside_them": round(b.phase["ntt"] / steps * 1e3, 3),

@@ -2,8 +2,9 @@
 line, the CPU baseline last.  One function per stage; every stage after the first measurement runs through run_leg (an exception costs the
 stage's fields, never the line) and, where a collective could hang, under the line's watchdog."""
 import os
+import sys
 
-from . import headline, legs_multi as M
+from . import dump, headline, legs_multi as M
 from .line import ResultLine, run_leg
 
 OPMIX_STEPS, OPMIX_WARMUP = 5, 2      # the op-mix step beside a proof headline: a short measurement of its own (`op_mix`), not the timed K steps
@@ -45,6 +46,14 @@ def _proof_fields(out, next_rows, class_row):
         out["proof_ms_class_prover_all_ranks"] = class_row["ms"]
 
 
+def _dump(b, out, what, arrays):
+    """--dump-outputs, rank 0, right after the timed region whose last step `arrays()` reads: the files and the line's `dump_outputs` field.  A failure
+    is written into that field (and ends the run with exit code 3 once the line is out), never into the measurement."""
+    if not (b.args.dump_outputs and b.rank == 0):
+        return
+    out["dump_outputs"] = run_leg(None, "dump_outputs", None, lambda: dump.write(b.args.dump_outputs, arrays(), what))
+
+
 
 def run(args, json_fd):
     from .run import Bench
@@ -66,6 +75,10 @@ def run(args, json_fd):
     out = headline.result_line(b, dt, phases_ms, om_steps, om_warm)
     guard.arm(None, 0)
     guard.out = out
+    if rank0 and args.dump_outputs:
+        out["dump_outputs"] = {"error": "the timed path did not complete its last step"}
+    if not proof_headline:
+        _dump(b, out, "op-mix step: this rank's outputs", lambda: dump.op_mix_arrays(b, b.last_step_out))
     if rank0:
         out["headline"] = ("op-mix step (SURVEY §8d)" if not proof_headline else
                            "op-mix step (SURVEY §8d) — FALLBACK: the proof loop has not completed (see proof_headline_error / aborted_optional_leg)")
@@ -98,6 +111,7 @@ def run(args, json_fd):
             dt_p, rounds_ms, kern_p, k_, w_ = res
             proof_ms = dt_p / k_ * 1e3
             if proof_headline:
+                _dump(b, out, "the last timed proof (prover.py)", lambda: dump.proof_arrays(P.proof))
                 headline.promote_proof(b, out, dt_p, rounds_ms, kern_p, k_, w_,
                                        "K verified five-round proofs of a satisfied synthetic circuit on one GPU (prover.py; dispatcher2.rs:192-713)", P.overlapped)
         if b.overlap or (P is not None and P.overlapped):
@@ -137,6 +151,8 @@ def run(args, json_fd):
             CP = M.ClassProof(b)                               # every rank raises or none does (same sizes everywhere)
             k_, w_ = (args.steps, args.warmup) if (proof_headline and not single) else (1, 0)
             dt_c, rounds_c, kern_c = headline.timed_proofs(b, guard, CP, k_, w_)
+            if proof_headline and not single:
+                _dump(b, out, "the last timed proof (class_prover.py)" + (", SIMULATED ranks" if sim else ""), lambda: dump.proof_arrays(CP.proof))
             row = CP.finish(dt_c / k_ * 1e3, rounds_c)
             return row, dt_c, rounds_c, kern_c, k_, w_, CP.overlapped
         res = run_leg(guard, "class_prover", 2 * LEG + 2.0 * args.steps, run_class)
@@ -180,5 +196,8 @@ def run(args, json_fd):
         guard.start_watchdog()
         out["cpu_baseline"] = run_leg(guard, "cpu_baseline", float(os.environ.get("PLONK_BENCH_CPU_BUDGET_S", "900")), lambda: cpu_baseline(args, cfg, host_bases))
     guard.emit()
+    if rank0 and "error" in (out.get("dump_outputs") or {}):
+        print("bench.py --dump-outputs: " + out["dump_outputs"]["error"], file=sys.stderr)
+        raise SystemExit(3)
 
 

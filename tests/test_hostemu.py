@@ -256,6 +256,32 @@ def test_bench_program_proof_only_sub_run(emu_env):
     assert set(var) == {"key_coset_ffts_inside_round_3"} and var["key_coset_ffts_inside_round_3"]["same_proof_as_the_verified_one"] is True, var
 
 
+@pytest.mark.parametrize("headline", ["proof", "op-mix"])
+def test_bench_dump_outputs_are_the_same_in_every_run(emu_env, tmp_path, headline):
+    """`bench.py --dump-outputs DIR`: the last timed step's outputs as float64 .npy files, identical in two runs with the same arguments (seeded
+    inputs) — what lets two builds be compared output for output.  The proof headline dumps the proof the verifier then accepts."""
+    import json
+    import numpy as np
+    e = dict(emu_env, HIPEMU_DEVICES="4", HIPEMU_THREADS=str(min(8, os.cpu_count() or 1)))
+    files = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--log-n", "7", "--headline", headline, "--no-next-rows",
+                            "--no-cpu-baseline", "--no-other-configs", "--dump-outputs", str(tmp_path / run)], cwd=ROOT, env=e,
+                           capture_output=True, text=True, timeout=900)
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert r.returncode == 0 and len(lines) == 1, (r.stdout + r.stderr)[-3000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 2 and d["verified"] is True and "error" not in d["dump_outputs"], d.get("dump_outputs")
+        files.append(d["dump_outputs"]["files"])
+        assert sorted(os.listdir(tmp_path / run)) == files[-1]
+    want = {"proof": {"wires_poly_comms_xy.npy", "split_quot_poly_comms_xy.npy", "wires_evals.npy", "opening_proof_xy.npy", "shifted_opening_proof_xy.npy"},
+            "op-mix": {"commitment_xy.npy", "intt_n_0.npy", "intt_n_6.npy", "coset_ifft_8n.npy"}}[headline]
+    assert files[0] == files[1] and want <= set(files[0]), files[0]
+    for f in files[0]:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b), f
+
+
 def test_differential_fuzz_slice(emu_env):
     """A fixed-seed slice of tools/fuzz_abi.py (random operations, shapes, flags and options against the oracle); long runs are a manual tool —
     nineteen operations, from single kernels to whole proofs handed to the verifier; under AddressSanitizer it found the two defects recorded in DESIGN §5 and docs/HISTORY.md §0."""
