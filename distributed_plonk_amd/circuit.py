@@ -1,0 +1,204 @@
+"""User circuits: from jellyfish's arithmetised form to a proving instance in HBM.
+
+A circuit is what jellyfish's `preprocess` consumes: for each of the 5 wire columns and each gate the variable the wire reads,
+a witness value per variable, the 13 selector columns and the public inputs.  `preprocess` turns it into what `Prover.load_key_dev`,
+`Prover.verifying_key` and `Prover.prove_dev` take — the same attribute names as `synthetic.SyntheticInstance`:
+
+    inst = preprocess(worker, Circuit(wire_vars, witness, selector_evals, public_inputs).pad(zero_var))
+    pv = Prover(worker, inst.log_n)
+    pv.load_key_dev(inst.sel_ptrs, inst.sig_ptrs, inst.k)
+    proof = pv.prove_dev(inst.wev, inst.d_id.ptr, inst.d_idx.ptr, inst.d_pi.ptr, blinders, pv.fiat_shamir(inst.public_inputs()))
+
+The work runs on the device: the copy-constraint permutation (plonk_circuit_permutation_dev), witness placement
+(plonk_circuit_witness_dev), the satisfiability check (plonk_circuit_check_dev) and the 13 + 5 inverse NTTs into coefficient form.
+Selector order: q_lc 0-3, q_mul 4-5, q_hash 6-9, q_o 10, q_c 11, q_ecc 12.  Field elements are (.., 4) u64 Montgomery limbs.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+
+from . import fr as _fr
+from .synthetic import NUM_SELECTORS, NUM_WIRE_TYPES, wire_subset_separators
+from .worker import PlonkWorker
+
+
+class UnsatisfiedCircuit(ValueError):
+    """The witness does not satisfy the circuit: `gate` is the first failing gate (or -1), `position` the first wire position
+    p = i * n + j whose value differs from the next position of its copy cycle (or -1)."""
+
+    def __init__(self, gate: int, position: int, n: int):
+        parts = []
+        if gate >= 0:
+            parts.append(f"gate {gate} does not satisfy its gate equation")
+        if position >= 0:
+            parts.append(f"copy constraint broken at position {position} (wire {position // n} of gate {position % n})")
+        super().__init__("; ".join(parts))
+        self.gate, self.position = gate, position
+
+
+def _fr_array(a, shape_tail, what: str) -> np.ndarray:
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    if a.shape[-len(shape_tail):] != shape_tail:
+        raise ValueError(f"{what}: shape {a.shape}, expected (..., {', '.join(map(str, shape_tail))})")
+    return a
+
+
+class Circuit:
+    """Host arrays of one circuit.
+
+    wire_vars: (5, gates) variable ids; witness: (num_vars, 4); selector_evals: (13, gates, 4) evaluations per gate;
+    public_inputs: (num_inputs, 4), the values that sit at gates 0 .. num_inputs (the IO-gate convention: such a gate reads
+    its variable on wire 4 with q_o = 1, so PI - e = 0); k: (5, 4) coset representatives, default
+    `synthetic.wire_subset_separators(field, 1)` of the worker's curve."""
+
+    def __init__(self, wire_vars, witness, selector_evals, public_inputs=None, k: Optional[np.ndarray] = None):
+        wv = np.asarray(wire_vars)
+        if wv.ndim != 2 or wv.shape[0] != NUM_WIRE_TYPES:
+            raise ValueError(f"wire_vars: shape {wv.shape}, expected ({NUM_WIRE_TYPES}, gates)")
+        gates = wv.shape[1]
+        if gates == 0:
+            raise ValueError("a circuit needs at least one gate")
+        witness = _fr_array(witness, (4,), "witness")
+        if witness.ndim != 2 or witness.shape[0] == 0:
+            raise ValueError(f"witness: shape {witness.shape}, expected (num_vars >= 1, 4)")
+        num_vars = witness.shape[0]
+        if wv.size and (wv.min() < 0 or wv.max() >= num_vars):
+            raise ValueError(f"wire_vars: ids must lie in [0, {num_vars})")
+        sel = _fr_array(selector_evals, (4,), "selector_evals")
+        if sel.shape != (NUM_SELECTORS, gates, 4):
+            raise ValueError(f"selector_evals: shape {sel.shape}, expected ({NUM_SELECTORS}, {gates}, 4)")
+        pub = np.zeros((0, 4), dtype=np.uint64) if public_inputs is None else _fr_array(public_inputs, (4,), "public_inputs").reshape(-1, 4)
+        if pub.shape[0] > gates:
+            raise ValueError(f"{pub.shape[0]} public inputs for {gates} gates")
+        if k is not None:
+            k = np.ascontiguousarray(k, dtype=np.uint64)
+            if k.shape != (NUM_WIRE_TYPES, 4):
+                raise ValueError(f"k: shape {k.shape}, expected ({NUM_WIRE_TYPES}, 4)")
+        self.wire_vars = np.ascontiguousarray(wv, dtype=np.uint32)
+        self.witness, self.selector_evals, self.public_inputs, self.k = witness, sel, pub, k
+
+    @property
+    def num_gates(self) -> int:
+        return self.wire_vars.shape[1]
+
+    @property
+    def num_vars(self) -> int:
+        return self.witness.shape[0]
+
+    def pad(self, zero_var: int) -> "Circuit":
+        """A copy with the gate count raised to the next power of two (>= 2), as jellyfish's padding does: the new gates have zero
+        selectors and all five wires read `zero_var`, whose witness value must be zero."""
+        if not 0 <= zero_var < self.num_vars:
+            raise ValueError(f"zero_var {zero_var} is not a variable of this circuit")
+        if self.witness[zero_var].any():
+            raise ValueError(f"zero_var {zero_var} has a nonzero witness value")
+        g = self.num_gates
+        n = max(2, 1 << (g - 1).bit_length())
+        wv = np.full((NUM_WIRE_TYPES, n), zero_var, dtype=np.uint32)
+        wv[:, :g] = self.wire_vars
+        sel = np.zeros((NUM_SELECTORS, n, 4), dtype=np.uint64)
+        sel[:, :g] = self.selector_evals
+        return Circuit(wv, self.witness.copy(), sel, self.public_inputs.copy(), None if self.k is None else self.k.copy())
+
+
+class PreprocessedCircuit:
+    """Device buffers of one preprocessed circuit; `close()` frees them.  Attribute names follow synthetic.SyntheticInstance, so
+    Prover.load_key_dev / verifying_key / prove_dev take it unchanged."""
+
+    def __init__(self, worker: PlonkWorker, n: int, num_inputs: int, k: np.ndarray):
+        self.w, self.n, self.num_inputs = worker, n, num_inputs
+        self.log_n = n.bit_length() - 1
+        self.k = np.ascontiguousarray(k, dtype=np.uint64)
+        self._bufs = []
+        alloc = lambda n_fr: self._keep(worker.alloc(n_fr * 32))
+        self.d_wires = alloc(NUM_WIRE_TYPES * n)
+        self.d_id = alloc(NUM_WIRE_TYPES * n)
+        self.d_idx = self._keep(worker.alloc(NUM_WIRE_TYPES * n * 8))
+        self.d_sig_ev = alloc(NUM_WIRE_TYPES * n)
+        self.d_sel = alloc(NUM_SELECTORS * n)
+        self.d_sig = alloc(NUM_WIRE_TYPES * n)
+        self.d_pi = alloc(n)
+        self.wev = [self.d_wires.ptr + i * n * 32 for i in range(NUM_WIRE_TYPES)]
+        self.sel_ptrs = [self.d_sel.ptr + t * n * 32 for t in range(NUM_SELECTORS)]
+        self.sig_ptrs = [self.d_sig.ptr + t * n * 32 for t in range(NUM_WIRE_TYPES)]
+
+    def _keep(self, b):
+        self._bufs.append(b)
+        return b
+
+    def public_inputs(self) -> np.ndarray:
+        """`circuit.public_input()`: the num_inputs values (not padded) -> (num_inputs, 4)."""
+        return self.d_pi.download((self.num_inputs, 4))
+
+    def download(self) -> dict:
+        """Everything as host arrays (small sizes only)."""
+        n = self.n
+        return dict(wires=self.d_wires.download((NUM_WIRE_TYPES, n, 4)), selectors=self.d_sel.download((NUM_SELECTORS, n, 4)),
+                    sigmas=self.d_sig.download((NUM_WIRE_TYPES, n, 4)), id_perm=self.d_id.download((NUM_WIRE_TYPES * n, 4)),
+                    perm_idx=self.d_idx.download((NUM_WIRE_TYPES * n,)), pub_input=self.d_pi.download((n, 4)), k=self.k.copy(),
+                    sigma_evals=self.d_sig_ev.download((NUM_WIRE_TYPES, n, 4)))
+
+    def close(self):
+        for b in self._bufs:
+            b.free()
+        self._bufs = []
+
+
+def default_k(curve_name: str) -> np.ndarray:
+    return wire_subset_separators(_fr.FIELDS[curve_name], 1)
+
+
+def preprocess_dev(worker: PlonkWorker, d_wire_vars: int, n: int, num_vars: int, d_witness: int, d_selector_evals: int, d_pub_input: int,
+                   num_inputs: int, k: Optional[np.ndarray] = None, check: bool = True) -> PreprocessedCircuit:
+    """`preprocess` for a circuit already in HBM: d_wire_vars u32 [5][n], d_witness num_vars Fr, d_selector_evals [13][n] Fr,
+    d_pub_input n Fr (public inputs at gates 0 .. num_inputs, zero elsewhere).  The caller's buffers are read, not modified or kept.
+    check: run the satisfiability check and raise UnsatisfiedCircuit naming the first failing gate / copy position."""
+    if n < 2 or n & (n - 1):
+        raise ValueError(f"gate count {n} is not a power of two >= 2: pad the circuit first (Circuit.pad)")
+    if not 0 <= num_inputs <= n:
+        raise ValueError(f"{num_inputs} public inputs for {n} gates")
+    w = worker
+    k = default_k(w.curve_name) if k is None else k
+    inst = PreprocessedCircuit(w, n, num_inputs, k)
+    try:
+        w.memcpy_d2d(inst.d_pi.ptr, d_pub_input, n * 32)
+        w.circuit_permutation_dev(d_wire_vars, n, num_vars, inst.k, inst.d_id.ptr, inst.d_idx.ptr, inst.d_sig_ev.ptr)
+        w.circuit_witness_dev(d_wire_vars, n, d_witness, num_vars, inst.d_wires.ptr)
+        if check:
+            gate, pos = w.circuit_check_dev(inst.d_wires.ptr, d_selector_evals, inst.d_pi.ptr, inst.d_idx.ptr, n)
+            if gate >= 0 or pos >= 0:
+                raise UnsatisfiedCircuit(gate, pos, n)
+        # proving key: selector and sigma polynomials in coefficient form (n-point iNTTs; ntt_dev consumes its input, so a copy goes in)
+        tmp = w.alloc(n * 32)
+        try:
+            for src, dst, cnt in ((d_selector_evals, inst.d_sel.ptr, NUM_SELECTORS), (inst.d_sig_ev.ptr, inst.d_sig.ptr, NUM_WIRE_TYPES)):
+                for t in range(cnt):
+                    w.memcpy_d2d_async(tmp.ptr, src + t * n * 32, n * 32)
+                    w.ntt_dev(tmp.ptr, dst + t * n * 32, n, True, False)
+            w.sync()
+        finally:
+            tmp.free()
+    except BaseException:
+        inst.close()
+        raise
+    return inst
+
+
+def preprocess(worker: PlonkWorker, circuit: Circuit, check: bool = True) -> PreprocessedCircuit:
+    """Upload a Circuit (gate count a power of two: Circuit.pad) and run preprocess_dev on it."""
+    n = circuit.num_gates
+    if n < 2 or n & (n - 1):
+        raise ValueError(f"gate count {n} is not a power of two >= 2: pad the circuit first (Circuit.pad)")
+    pub = np.zeros((n, 4), dtype=np.uint64)
+    pub[:circuit.public_inputs.shape[0]] = circuit.public_inputs
+    w = worker
+    bufs = []
+    try:
+        up = lambda a: bufs.append(w.alloc(max(a.nbytes, 8)).upload(a)) or bufs[-1].ptr
+        d_vars, d_wit, d_sel, d_pub = up(circuit.wire_vars), up(circuit.witness), up(circuit.selector_evals), up(pub)
+        return preprocess_dev(w, d_vars, n, circuit.num_vars, d_wit, d_sel, d_pub, circuit.public_inputs.shape[0], circuit.k, check)
+    finally:
+        for b in bufs:
+            b.free()

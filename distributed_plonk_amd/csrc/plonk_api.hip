@@ -1200,6 +1200,53 @@ extern "C" int plonk_synth_circuit(plonk_ctx* ctx, uint64_t seed, size_t n, size
     return synth_circuit_dev(ctx->curve, seed, n, num_inputs, k, w, d_wires, d_selector_evals, d_sigma_evals, d_id_perm, d_perm_idx, d_pub_input,
                              ctx->stream);
 }
+// gate count of a user circuit: a power of two >= 2 within the two-adicity, and 5n positions addressable by the 32-bit sort payload
+static int circuit_domain(plonk_ctx* ctx, size_t n, const char* who, Fr* omega) {
+    if (n < 2 || (n & (n - 1))) return plonk_fail(PLONK_ERR_DOMAIN, "%s: n = %zu is not a power of two >= 2", who, n);
+    int log_n = 0;
+    while (((size_t)1 << log_n) < n) log_n++;
+    if (log_n > ctx->tables.two_adicity) return plonk_fail(PLONK_ERR_DOMAIN, "%s: 2^%d exceeds the two-adicity %d", who, log_n, ctx->tables.two_adicity);
+    if (5 * (uint64_t)n > 0xFFFFFFFFull) return plonk_fail(PLONK_ERR_DOMAIN, "%s: 5n = %llu wire positions exceed 2^32 - 1", who, 5ull * n);
+    if (omega) {
+        Fr w = ctx->tables.h_root[0];
+        for (int i = log_n; i < ctx->tables.two_adicity; i++) w = fp_sqr(w, ctx->tables.fp);
+        *omega = w;
+    }
+    return PLONK_OK;
+}
+extern "C" int plonk_circuit_permutation_dev(plonk_ctx* ctx, const void* d_wire_vars, size_t n, size_t num_vars, const uint64_t* k, void* d_id_perm,
+                                             void* d_perm_idx, void* d_sigma_evals) {
+    CHECK_CTX(ctx);
+    if (!d_wire_vars || !k || !d_id_perm || !d_perm_idx || !d_sigma_evals) return plonk_fail(PLONK_ERR_ARG, "plonk_circuit_permutation_dev: null");
+    Fr omega;
+    int rc = circuit_domain(ctx, n, "plonk_circuit_permutation_dev", &omega);
+    if (rc) return rc;
+    if (num_vars == 0 || num_vars > ((size_t)1 << 32))
+        return plonk_fail(PLONK_ERR_ARG, "plonk_circuit_permutation_dev: num_vars = %zu (ids are u32: 1 .. 2^32)", num_vars);
+    if ((rc = ensure_scratch2(ctx, circuit_permutation_scratch_bytes(n, num_vars)))) return rc;
+    return circuit_permutation_run(ctx->curve, (const uint32_t*)d_wire_vars, n, num_vars, k, omega, (Fr*)d_id_perm, (uint64_t*)d_perm_idx, (Fr*)d_sigma_evals,
+                                   ctx->d_scratch2, ctx->stream);
+}
+extern "C" int plonk_circuit_witness_dev(plonk_ctx* ctx, const void* d_wire_vars, size_t n, const void* d_witness, size_t num_vars, void* d_wires) {
+    CHECK_CTX(ctx);
+    if (!d_wire_vars || !d_witness || !d_wires) return plonk_fail(PLONK_ERR_ARG, "plonk_circuit_witness_dev: null");
+    int rc = circuit_domain(ctx, n, "plonk_circuit_witness_dev", nullptr);
+    if (rc) return rc;
+    if (num_vars == 0) return plonk_fail(PLONK_ERR_ARG, "plonk_circuit_witness_dev: num_vars = 0");
+    if ((rc = ensure_scratch2(ctx, 64))) return rc;
+    return circuit_witness_run((const uint32_t*)d_wire_vars, n, (const Fr*)d_witness, num_vars, (Fr*)d_wires, ctx->d_scratch2, ctx->stream);
+}
+extern "C" int plonk_circuit_check_dev(plonk_ctx* ctx, const void* d_wires, const void* d_selector_evals, const void* d_pub_input, const void* d_perm_idx,
+                                       size_t n, int64_t* first_bad_gate, int64_t* first_bad_copy) {
+    CHECK_CTX(ctx);
+    if (!d_wires || !d_selector_evals || !d_pub_input || !first_bad_gate || !first_bad_copy)
+        return plonk_fail(PLONK_ERR_ARG, "plonk_circuit_check_dev: null");
+    int rc = circuit_domain(ctx, n, "plonk_circuit_check_dev", nullptr);
+    if (rc) return rc;
+    if ((rc = ensure_scratch2(ctx, 64))) return rc;
+    return circuit_check_run(ctx->curve, (const Fr*)d_wires, (const Fr*)d_selector_evals, (const Fr*)d_pub_input, (const uint64_t*)d_perm_idx, n,
+                             first_bad_gate, first_bad_copy, ctx->d_scratch2, ctx->stream);
+}
 extern "C" int plonk_debug_field_op(plonk_ctx* ctx, int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
     CHECK_CTX(ctx);
     if (!a || !out) return plonk_fail(PLONK_ERR_ARG, "plonk_debug_field_op: null");

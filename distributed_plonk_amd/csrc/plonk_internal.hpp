@@ -218,6 +218,15 @@ int synth_circuit_dev(int curve, uint64_t seed, size_t n, size_t num_inputs, con
 
 const FrParams& fr_params(int curve);
 
+// circuit preprocessing (circuit_kernels.hpp, built in synth.hip): the copy-constraint permutation from gate wiring, witness placement
+// and the satisfiability check.  scratch: circuit_permutation_scratch_bytes for the permutation, 64 bytes for the other two.
+size_t circuit_permutation_scratch_bytes(size_t n, size_t num_vars);
+int circuit_permutation_run(int curve, const uint32_t* wire_vars, size_t n, size_t num_vars, const uint64_t* k_mont, const Fr& omega_n,
+                            Fr* id_perm, uint64_t* perm_idx, Fr* sigma, void* scratch, hipStream_t stream);
+int circuit_witness_run(const uint32_t* wire_vars, size_t n, const Fr* witness, size_t num_vars, Fr* wires, void* scratch, hipStream_t stream);
+int circuit_check_run(int curve, const Fr* wires, const Fr* sel, const Fr* pub, const uint64_t* perm_idx, size_t n, int64_t* first_bad_gate,
+                      int64_t* first_bad_copy, void* scratch, hipStream_t stream);
+
 // ----------------------------------------------------------------------------------------------- O(n) prover steps (poly_ops.hip, quotient.hip)
 int quotient_evals_run(NttTables& T, const plonk_quotient_inputs* in, size_t n, size_t m, const uint64_t* alpha, const uint64_t* beta,
                        const uint64_t* gamma, const uint64_t* k, uint32_t cls_stride, uint32_t cls_offset, void* d_out, hipStream_t stream);

@@ -354,3 +354,7 @@ int synth_circuit_dev(int curve, uint64_t seed, size_t n, size_t num_inputs, con
     if (e != hipSuccess) return plonk_fail(PLONK_ERR_HIP, "synth_circuit launch: %s", hipGetErrorString(e));
     return PLONK_OK;
 }
+
+// ---------------------------------------------------------------------------------------------- user circuits
+// preprocessing of circuits given as gate wiring (jellyfish's arithmetised form): kernels and launchers live in their own header
+#include "circuit_kernels.hpp"

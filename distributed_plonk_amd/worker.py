@@ -395,6 +395,22 @@ class PlonkWorker:
         check(self.lib.plonk_synth_circuit(self.ctx, seed, n, num_inputs, _ptr(_u64(k)), d_wires, d_sel_evals, d_sigma_evals, d_id_perm, d_perm_idx,
                                            d_pub_input))
 
+    # ------------------------------------------------------------------ user circuits (distributed_plonk_amd/circuit.py)
+    def circuit_permutation_dev(self, d_wire_vars: int, n: int, num_vars: int, k: np.ndarray, d_id_perm: int, d_perm_idx: int, d_sigma_evals: int):
+        """The copy-constraint permutation of a gate wiring (include/plonk_hip.h: plonk_circuit_permutation_dev).  d_wire_vars: u32 [5][n];
+        out: id_perm (5n Fr), perm_idx (5n u64), sigma evaluations (5n Fr)."""
+        check(self.lib.plonk_circuit_permutation_dev(self.ctx, d_wire_vars, n, num_vars, _ptr(_u64(k)), d_id_perm, d_perm_idx, d_sigma_evals))
+
+    def circuit_witness_dev(self, d_wire_vars: int, n: int, d_witness: int, num_vars: int, d_wires: int):
+        """wires[p] = witness[wire_vars[p]] (plonk_circuit_witness_dev)."""
+        check(self.lib.plonk_circuit_witness_dev(self.ctx, d_wire_vars, n, d_witness, num_vars, d_wires))
+
+    def circuit_check_dev(self, d_wires: int, d_selector_evals: int, d_pub_input: int, d_perm_idx: Optional[int], n: int):
+        """-> (first failing gate, first position p with wires[p] != wires[perm_idx[p]]), -1 for none (plonk_circuit_check_dev)."""
+        gate, copy = C.c_int64(0), C.c_int64(0)
+        check(self.lib.plonk_circuit_check_dev(self.ctx, d_wires, d_selector_evals, d_pub_input, d_perm_idx or None, n, C.byref(gate), C.byref(copy)))
+        return gate.value, copy.value
+
     def field_op(self, field: int, op: int, a: np.ndarray, b: Optional[np.ndarray] = None) -> np.ndarray:
         a = _u64(a)
         b = _u64(b) if b is not None else None

@@ -317,6 +317,31 @@ int plonk_synth_srs(plonk_ctx* ctx, const uint64_t* tau, size_t n, void* d_out);
  * (extended_id_permutation), perm_idx [5n] u64 (perm_i * n + perm_j), pub_input [n].  k: vk.k[0..5], host Fr. */
 int plonk_synth_circuit(plonk_ctx* ctx, uint64_t seed, size_t n, size_t num_inputs, const uint64_t* k, void* d_wires, void* d_selector_evals,
                         void* d_sigma_evals, void* d_id_perm, void* d_perm_idx, void* d_pub_input);
+/* Preprocessing of a user circuit given as jellyfish's arithmetised form (wire_variables, witness, selectors, public inputs).
+ * Device pointers, host Fr in Montgomery form, ordered on the context's stream.  n: the gate count, a power of two >= 2 within the
+ * field's two-adicity (PLONK_ERR_DOMAIN otherwise).  Positions are p = i*n + j (wire column i < 5, gate j < n).  Ids are checked on the
+ * device before any of them is used as an index: an out-of-range id returns PLONK_ERR_ARG naming the first offending position, and
+ * nothing is read or written out of bounds.
+ *
+ * The copy-constraint permutation (jellyfish compute_wire_permutation).  wire_vars: u32 [5][n], wire_vars[i*n + j] = the variable
+ * gate j's wire i reads, each < num_vars; k: vk.k[0..5] (5 x 4 u64).  The positions of one variable, in increasing order, form a
+ * cycle whose last position links back to the first (a variable read once maps its position to itself):
+ *   id_perm [5n] Fr:   id_perm[i*n + j] = k_i * w^j
+ *   perm_idx [5n] u64: the position after p in the cycle of p's variable
+ *   sigma_evals [5n] Fr: id_perm[perm_idx[p]]  (the 5 sigma polynomials in evaluation form)
+ * Bit-identical from run to run (a stable device radix sort of (variable, position), then a linking pass).  Scratch from the context
+ * (2 x 2 x 5n u32 + 4 * num_vars bytes), given back by plonk_trim.  Returns once the work is enqueued. */
+int plonk_circuit_permutation_dev(plonk_ctx* ctx, const void* d_wire_vars, size_t n, size_t num_vars, const uint64_t* k, void* d_id_perm,
+                                  void* d_perm_idx, void* d_sigma_evals);
+/* Witness placement: wires[p] = witness[wire_vars[p]], p < 5n; witness: num_vars Fr.  Synchronises (reads the id check's verdict). */
+int plonk_circuit_witness_dev(plonk_ctx* ctx, const void* d_wire_vars, size_t n, const void* d_witness, size_t num_vars, void* d_wires);
+/* Satisfiability (jellyfish check_circuit_satisfiability).  wires [5][n], selector_evals [13][n] (q_lc 0-3, q_mul 4-5, q_hash 6-9, q_o 10,
+ * q_c 11, q_ecc 12), pub_input [n] evaluations.  *first_bad_gate = the smallest gate j where
+ *   q_c + PI + sum q_lc*w + q_mul0*ab + q_mul1*cd + sum q_hash*w^5 + q_ecc*abcde - q_o*e != 0, or -1.
+ * perm_idx [5n] u64 or NULL: *first_bad_copy = the smallest position p with wires[p] != wires[perm_idx[p]], or -1 (always -1 without
+ * perm_idx); an entry >= 5n returns PLONK_ERR_ARG.  Synchronises. */
+int plonk_circuit_check_dev(plonk_ctx* ctx, const void* d_wires, const void* d_selector_evals, const void* d_pub_input, const void* d_perm_idx,
+                            size_t n, int64_t* first_bad_gate, int64_t* first_bad_copy);
 /* Use n_bases points already in HBM (PLONK_BASES_XY) as the SRS without a host round trip; they are
  * re-encoded into the library's resident form (x || y as canonical R'-Montgomery residues in 32-bit words: 64 B / 96 B per point), the caller keeps its buffer. */
 int plonk_init_dev(plonk_ctx* ctx, const void* d_bases_xy, size_t n_bases, size_t domain_size,
