@@ -50,6 +50,11 @@ class QuotientInputs(C.Structure):   # include/plonk_hip.h plonk_quotient_inputs
                 ("perm", C.c_void_p), ("pub_input", C.c_void_p)]
 
 
+class VerifyKey(C.Structure):      # include/plonk_hip.h plonk_verify_key
+    _fields_ = [("domain_size", C.c_uint64), ("num_inputs", C.c_uint64), ("k", (C.c_uint64 * 4) * 5), ("d_comms", C.c_void_p),
+                ("transcript_state", C.c_uint8 * 200), ("transcript_pos", C.c_uint32 * 3)]
+
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
 
 # name -> (restype, argtypes); every symbol include/plonk_hip.h declares
@@ -99,6 +104,12 @@ SIGNATURES = {
     "plonk_circuit_witness_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "plonk_circuit_check_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64),
                                           C.POINTER(C.c_int64)]),
+    "plonk_g2_generator": (C.c_int, [C.c_int, C.c_void_p]),
+    "plonk_g2_mul": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "plonk_g2_check": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
+    "plonk_pairing_check": (C.c_int, [C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "plonk_verify_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(VerifyKey), C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
     "plonk_init_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t]),
     "plonk_debug_field_op": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "plonk_quotient_evals_dev": (C.c_int, [C.c_void_p, C.POINTER(QuotientInputs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

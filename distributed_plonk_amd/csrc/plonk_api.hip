@@ -11,6 +11,7 @@
 #include "constants.h"
 #include "ec.hpp"
 #include "plonk_internal.hpp"
+#include "pairing.hpp"
 
 
 // ---------------------------------------------------------------------------------------------- errors
@@ -1261,3 +1262,156 @@ extern "C" int plonk_debug_field_op(plonk_ctx* ctx, int field, int op, const uin
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return PLONK_OK;
 }
+
+// ---------------------------------------------------------------------------------------------- G2, the pairing, batched verification
+// Host-only like plonk_g1_add: G2 points as x.c0 || x.c1 || y.c0 || y.c1 Montgomery limbs (all zero = infinity), G1 as x || y (0, 0 = infinity).
+template <int N> static int g2_load(const uint64_t* in, pairing::G2<N>& q, const char* what) {
+    const pairing::Curve<N>& C = pairing::curve<N>();
+    const uint32_t* w = (const uint32_t*)in;
+    uint32_t any = 0;
+    for (int i = 0; i < 4 * N; i++) any |= w[i];
+    Fp<N> c[4];
+    for (int i = 0; i < 4; i++) {
+        c[i] = fp_from_limbs<N>(w + i * N);
+        bool lt = false;
+        for (int j = N - 1; j >= 0; j--)
+            if (c[i].l[j] != C.P->p[j]) { lt = c[i].l[j] < C.P->p[j]; break; }
+        if (!lt) return plonk_fail(PLONK_ERR_ARG, "%s: a coordinate is not a canonical residue", what);
+    }
+    q.x = {c[0], c[1]};
+    q.y = {c[2], c[3]};
+    q.inf = any == 0;
+    if (!pairing::g2_on_curve(q, C)) return plonk_fail(PLONK_ERR_ARG, "%s: point is not on the twist", what);
+    return PLONK_OK;
+}
+template <int N> static void g2_store(const pairing::G2<N>& q, uint64_t* out) {
+    uint32_t* w = (uint32_t*)out;
+    const Fp<N> c[4] = {q.x.c0, q.x.c1, q.y.c0, q.y.c1};
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < N; j++) w[i * N + j] = q.inf ? 0 : c[i].l[j];
+}
+template <int N> static int g2_mul_t(const uint64_t* scalar, const uint64_t* in, uint64_t* out) {
+    const pairing::Curve<N>& C = pairing::curve<N>();
+    pairing::G2<N> q;
+    int rc = g2_load<N>(in, q, "plonk_g2_mul");
+    if (rc) return rc;
+    const Fr s = fp_from_mont(fp_from_limbs<8>((const uint32_t*)scalar), *C.R);
+    g2_store<N>(pairing::g2_mul(q, s.l, 8, C), out);
+    return PLONK_OK;
+}
+template <int N> static int g2_check_t(const uint64_t* pt, int* ok) {
+    pairing::G2<N> q;
+    const uint32_t* w = (const uint32_t*)pt;
+    const FpParams<N>& P = *pairing::curve<N>().P;
+    for (int i = 0; i < 4; i++) {          // not canonical or not on the twist: *ok = 0 (a verdict, not an argument error)
+        bool lt = false;
+        for (int j = N - 1; j >= 0; j--)
+            if (w[i * N + j] != P.p[j]) { lt = w[i * N + j] < P.p[j]; break; }
+        if (!lt) { *ok = 0; return PLONK_OK; }
+    }
+    uint32_t any = 0;
+    for (int i = 0; i < 4 * N; i++) any |= w[i];
+    q.x = {fp_from_limbs<N>(w), fp_from_limbs<N>(w + N)};
+    q.y = {fp_from_limbs<N>(w + 2 * N), fp_from_limbs<N>(w + 3 * N)};
+    q.inf = any == 0;
+    *ok = pairing::g2_check(q, pairing::curve<N>()) ? 1 : 0;
+    return PLONK_OK;
+}
+template <int N> static int pairing_check_t(size_t k, const uint64_t* g1_xy, const uint64_t* g2_xy, int* is_one) {
+    const pairing::Curve<N>& C = pairing::curve<N>();
+    const FpParams<N>& P = *C.P;
+    pairing::Fq12<N> f = pairing::f12_one(P);
+    for (size_t i = 0; i < k; i++) {
+        const uint32_t* w = (const uint32_t*)(g1_xy + i * (N / 2) * 2);
+        const Fp<N> x = fp_from_limbs<N>(w), y = fp_from_limbs<N>(w + N);
+        pairing::G2<N> q;
+        int rc = g2_load<N>(g2_xy + i * (N / 2) * 4, q, "plonk_pairing_check");
+        if (rc) return rc;
+        const bool p_inf = fp_is_zero(x) && fp_is_zero(y);
+        if (!p_inf) {
+            bool canon = true;
+            for (const Fp<N>* c : {&x, &y}) {
+                bool lt = false;
+                for (int j = N - 1; j >= 0; j--)
+                    if (c->l[j] != P.p[j]) { lt = c->l[j] < P.p[j]; break; }
+                canon = canon && lt;
+            }
+            const Fp<N> b = fp_from_limbs<N>(N == 8 ? BN254_G1_B_MONT : BLS12_381_G1_B_MONT);
+            if (!canon || !fp_eq(fp_sqr(y, P), fp_add(fp_mul(fp_sqr(x, P), x, P), b, P)))
+                return plonk_fail(PLONK_ERR_ARG, "plonk_pairing_check: G1 point %zu is not on the curve", i);
+        }
+        if (p_inf || q.inf) continue;                      // e(O, Q) = e(P, O) = 1
+        f = pairing::f12_mul(f, pairing::miller_loop(x, y, q, C), C);
+    }
+    *is_one = pairing::f12_eq(pairing::final_exponentiation(f, C), pairing::f12_one(P)) ? 1 : 0;
+    return PLONK_OK;
+}
+
+extern "C" int plonk_g2_generator(int curve, uint64_t* out) {
+    if (!out) return plonk_fail(PLONK_ERR_ARG, "plonk_g2_generator: null");
+    if (curve == PLONK_BN254) { const auto& C = pairing::curve<8>(); g2_store<8>({C.gx, C.gy, false}, out); return PLONK_OK; }
+    if (curve == PLONK_BLS12_381) { const auto& C = pairing::curve<12>(); g2_store<12>({C.gx, C.gy, false}, out); return PLONK_OK; }
+    return plonk_fail(PLONK_ERR_ARG, "plonk_g2_generator: unknown curve %d", curve);
+}
+extern "C" int plonk_g2_mul(int curve, const uint64_t* scalar, const uint64_t* in, uint64_t* out) {
+    if (!scalar || !in || !out) return plonk_fail(PLONK_ERR_ARG, "plonk_g2_mul: null");
+    if (curve == PLONK_BN254) return g2_mul_t<8>(scalar, in, out);
+    if (curve == PLONK_BLS12_381) return g2_mul_t<12>(scalar, in, out);
+    return plonk_fail(PLONK_ERR_ARG, "plonk_g2_mul: unknown curve %d", curve);
+}
+extern "C" int plonk_g2_check(int curve, const uint64_t* pt, int* ok) {
+    if (!pt || !ok) return plonk_fail(PLONK_ERR_ARG, "plonk_g2_check: null");
+    if (curve == PLONK_BN254) return g2_check_t<8>(pt, ok);
+    if (curve == PLONK_BLS12_381) return g2_check_t<12>(pt, ok);
+    return plonk_fail(PLONK_ERR_ARG, "plonk_g2_check: unknown curve %d", curve);
+}
+extern "C" int plonk_pairing_check(int curve, size_t k, const uint64_t* g1_xy, const uint64_t* g2_xy, int* is_one) {
+    if (!is_one || (k && (!g1_xy || !g2_xy))) return plonk_fail(PLONK_ERR_ARG, "plonk_pairing_check: null");
+    if (k > 4096) return plonk_fail(PLONK_ERR_ARG, "plonk_pairing_check: %zu pairs", k);
+    if (curve == PLONK_BN254) return pairing_check_t<8>(k, g1_xy, g2_xy, is_one);
+    if (curve == PLONK_BLS12_381) return pairing_check_t<12>(k, g1_xy, g2_xy, is_one);
+    return plonk_fail(PLONK_ERR_ARG, "plonk_pairing_check: unknown curve %d", curve);
+}
+
+extern "C" int plonk_verify_batch_dev(plonk_ctx* ctx, const plonk_verify_key* vk, size_t k, const void* d_proofs, const void* d_pub_inputs, const void* d_rho,
+                                      void* d_out_points, void* d_status, void* d_debug) {
+    CHECK_CTX(ctx);
+    if (!vk || !vk->d_comms) return plonk_fail(PLONK_ERR_ARG, "plonk_verify_batch_dev: null verifying key");
+    if (k == 0) return PLONK_OK;
+    if (k > (1u << 22)) return plonk_fail(PLONK_ERR_ARG, "plonk_verify_batch_dev: %zu proofs (at most 2^22 per call)", k);
+    if (!d_proofs || !d_rho || !d_out_points || !d_status || (vk->num_inputs && !d_pub_inputs))
+        return plonk_fail(PLONK_ERR_ARG, "plonk_verify_batch_dev: null device buffer");
+    const int log_n = ilog2_exact(vk->domain_size);
+    if (log_n < 1) return plonk_fail(PLONK_ERR_DOMAIN, "plonk_verify_batch_dev: domain size %llu is not a power of two >= 2", (unsigned long long)vk->domain_size);
+    if (log_n > (ctx->curve == PLONK_BN254 ? BN254_FR_TWO_ADICITY : BLS12_381_FR_TWO_ADICITY))
+        return plonk_fail(PLONK_ERR_DOMAIN, "plonk_verify_batch_dev: 2^%d exceeds the two-adicity", log_n);
+    if (vk->num_inputs > vk->domain_size) return plonk_fail(PLONK_ERR_ARG, "plonk_verify_batch_dev: %llu public inputs for %llu gates",
+                                                            (unsigned long long)vk->num_inputs, (unsigned long long)vk->domain_size);
+    if (vk->transcript_pos[0] >= 166 || vk->transcript_pos[1] > 166 || vk->transcript_pos[2] > 63)
+        return plonk_fail(PLONK_ERR_ARG, "plonk_verify_batch_dev: transcript position outside the STROBE rate");
+    const bool bn = ctx->curve == PLONK_BN254;
+    const FpParams<8>& R = bn ? BN254_FR_PARAMS : BLS12_381_FR_PARAMS;
+    const int two_adicity = bn ? BN254_FR_TWO_ADICITY : BLS12_381_FR_TWO_ADICITY;
+    for (int i = 0; i < 5; i++) {
+        bool lt = false;
+        const uint32_t* w = (const uint32_t*)vk->k[i];
+        for (int j = 7; j >= 0; j--)
+            if (w[j] != R.p[j]) { lt = w[j] < R.p[j]; break; }
+        if (!lt) return plonk_fail(PLONK_ERR_ARG, "plonk_verify_batch_dev: k[%d] is not a canonical residue", i);
+    }
+    Fr w = fp_from_limbs<8>(bn ? BN254_FR_TWO_ADIC_ROOT_MONT : BLS12_381_FR_TWO_ADIC_ROOT_MONT);     // primitive 2^two_adicity-th root, squared down to order n
+    for (int i = log_n; i < two_adicity; i++) w = fp_sqr(w, R);
+    Fr n_fr = fp_zero<8>();
+    n_fr.l[0] = (uint32_t)vk->domain_size;
+    n_fr.l[1] = (uint32_t)(vk->domain_size >> 32);
+    n_fr = fp_to_mont(n_fr, R);
+    int rc = ensure_scratch2(ctx, verify_batch_scratch_bytes(k));
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    rc = verify_batch_run(ctx->curve, vk->transcript_state, vk->transcript_pos, (size_t)log_n, (size_t)vk->num_inputs, &vk->k[0][0], w, n_fr, d_proofs,
+                          vk->d_comms, d_pub_inputs, d_rho, k, d_out_points, d_status, d_debug, ctx->d_scratch2, ctx->stream);
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    ctx->ev_valid = true;
+    return rc;
+}
+

@@ -220,6 +220,12 @@ const FrParams& fr_params(int curve);
 
 // circuit preprocessing (circuit_kernels.hpp, built in synth.hip): the copy-constraint permutation from gate wiring, witness placement
 // and the satisfiability check.  scratch: circuit_permutation_scratch_bytes for the permutation, 64 bytes for the other two.
+// batched proof verification (verify_kernels.hpp, built in synth.hip): per-proof checks, transcript, scalars and the two points of the folded
+// pairing check.  strobe_pos3: pos, pos_begin, cur_flags of the transcript state.  scratch: verify_batch_scratch_bytes(k).
+size_t verify_batch_scratch_bytes(size_t k);
+int verify_batch_run(int curve, const uint8_t* strobe, const uint32_t* strobe_pos3, size_t log_n, size_t num_inputs, const uint64_t* k_mont,
+                     const Fr& omega, const Fr& n_fr, const void* d_proofs, const void* d_vk_pts, const void* d_pub, const void* d_rho, size_t k,
+                     void* d_out, void* d_status, void* d_debug, void* scratch, hipStream_t stream);
 size_t circuit_permutation_scratch_bytes(size_t n, size_t num_vars);
 int circuit_permutation_run(int curve, const uint32_t* wire_vars, size_t n, size_t num_vars, const uint64_t* k_mont, const Fr& omega_n,
                             Fr* id_perm, uint64_t* perm_idx, Fr* sigma, void* scratch, hipStream_t stream);

@@ -1,0 +1,270 @@
+"""Verifying proofs without the SRS trapdoor: jf-plonk's `verify` / `batch_verify` (the pairing check e(A, [tau]_2) = e(B, [1]_2)).
+
+The per-proof work runs on the device, all proofs of a batch in parallel (`plonk_verify_batch_dev`): input checks, the Fiat-Shamir replay,
+the ~30 scalars of the linearised check and the two multi-scalar sums rho_k * A_k, rho_k * B_k with
+
+    A = W_zeta + u W_zeta_omega,   B = zeta W_zeta + u zeta w W_zeta_omega + F + u [z] - (E + u z(zeta w)) G.
+
+The host adds the K pairs and runs ONE two-pairing check e(sum rho A, beta H) * e(-sum rho B, H) == 1 (`plonk_pairing_check`); a failed
+batch is bisected, so f bad proofs cost O(f log K) pairing checks.  rho_k are drawn from `secrets` unless a seed is given (tests).
+
+The transcript labels of the two opening proofs and of u (b"open_proof", b"shifted_open_proof", b"u") are those of jf-plonk's verifier as
+far as the public sources show; like the serialised `Proof` layout they are not pinned by a reference-generated proof.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import random
+import secrets
+from typing import Optional, Sequence
+
+import numpy as np
+
+from . import _ffi
+from . import fr as _fr
+from .transcript import FQ_MODULI, PlonkTranscript
+
+NPTS, NEVALS = 13, 10
+STATUS_BITS = {1: "point off the curve", 2: "point outside the r-subgroup", 4: "zeta in the evaluation domain", 8: "non-canonical encoding"}
+
+_G1_GEN = {"bn254": (1, 2),
+           "bls12_381": (0x17f1d3a73197d7942695638c4fa9ac0fc3688c4f9774b905a14e3a3f171bac586c55e83ff97a1aeffb3af00adb22c6bb,
+                         0x08b3f481e3aaa0f1a09e30ed741d8ae4fcf5e095d5d00af600db18cb2c04b3edd03cc744a2888ae40caa232946c5e7e1)}
+
+
+def _q64(curve: str) -> int:
+    return _ffi.FQ_LIMBS64[_ffi.CURVES[curve]]
+
+
+def _fq_mont(curve: str, x: int) -> list:
+    q, n = FQ_MODULI[curve], _q64(curve)
+    v = x * pow(2, 64 * n, q) % q
+    return [(v >> (64 * i)) & (2 ** 64 - 1) for i in range(n)]
+
+
+def g1_generator(curve: str) -> np.ndarray:
+    x, y = _G1_GEN[curve]
+    return np.array(_fq_mont(curve, x) + _fq_mont(curve, y), dtype=np.uint64)
+
+
+def _g1_neg(curve: str, xy: np.ndarray) -> np.ndarray:
+    n = _q64(curve)
+    if not xy.any():
+        return xy.copy()
+    q = FQ_MODULI[curve]
+    y = sum(int(v) << (64 * i) for i, v in enumerate(xy[n:]))
+    ny = (q - y) % q
+    return np.concatenate([xy[:n], np.array([(ny >> (64 * i)) & (2 ** 64 - 1) for i in range(n)], dtype=np.uint64)])
+
+
+def _point_xy(curve: str, pt) -> np.ndarray:
+    """(xy limbs, is_infinity) as Prover / g1_to_affine return it -> x || y with (0, 0) for infinity."""
+    xy, inf = pt
+    return np.zeros(2 * _q64(curve), np.uint64) if inf else np.ascontiguousarray(xy, dtype=np.uint64).reshape(-1)
+
+
+def _lib():
+    return _ffi.lib()
+
+
+def g2_generator(curve: str) -> np.ndarray:
+    out = np.zeros(4 * _q64(curve), np.uint64)
+    _ffi.check(_lib().plonk_g2_generator(_ffi.CURVES[curve], out.ctypes.data))
+    return out
+
+
+def g2_mul(curve: str, scalar_mont, pt: np.ndarray) -> np.ndarray:
+    s = np.ascontiguousarray(scalar_mont, dtype=np.uint64)
+    pt = np.ascontiguousarray(pt, dtype=np.uint64)
+    out = np.zeros(4 * _q64(curve), np.uint64)
+    _ffi.check(_lib().plonk_g2_mul(_ffi.CURVES[curve], s.ctypes.data, pt.ctypes.data, out.ctypes.data))
+    return out
+
+
+def g2_check(curve: str, pt: np.ndarray) -> bool:
+    pt = np.ascontiguousarray(pt, dtype=np.uint64)
+    ok = C.c_int(0)
+    _ffi.check(_lib().plonk_g2_check(_ffi.CURVES[curve], pt.ctypes.data, C.byref(ok)))
+    return bool(ok.value)
+
+
+def pairing_check(curve: str, g1_points: Sequence[np.ndarray], g2_points: Sequence[np.ndarray]) -> bool:
+    """prod e(P_i, Q_i) == 1.  G1 as x || y, G2 as x.c0 || x.c1 || y.c0 || y.c1 (Montgomery limbs; all zero = infinity)."""
+    a = np.ascontiguousarray(np.concatenate([np.asarray(p, np.uint64).reshape(-1) for p in g1_points]))
+    b = np.ascontiguousarray(np.concatenate([np.asarray(q, np.uint64).reshape(-1) for q in g2_points]))
+    r = C.c_int(0)
+    _ffi.check(_lib().plonk_pairing_check(_ffi.CURVES[curve], len(g1_points), a.ctypes.data, b.ctypes.data, C.byref(r)))
+    return bool(r.value)
+
+
+class OpenKey:
+    """jf-plonk's verifier parameters (UnivariateVerifierParam): g = [1]_1, h = [1]_2, beta_h = [tau]_2.  The G2 points are checked to lie
+    on the twist in the order-r subgroup when the key is built."""
+
+    def __init__(self, curve: str, g: np.ndarray, h: np.ndarray, beta_h: np.ndarray):
+        self.curve = curve
+        self.g = np.ascontiguousarray(g, dtype=np.uint64).reshape(-1)
+        self.h = np.ascontiguousarray(h, dtype=np.uint64).reshape(-1)
+        self.beta_h = np.ascontiguousarray(beta_h, dtype=np.uint64).reshape(-1)
+        if not np.array_equal(self.g, g1_generator(curve)):
+            raise ValueError("OpenKey: g must be the G1 generator the prover's commitments and the device verifier use")
+        for name, pt in (("h", self.h), ("beta_h", self.beta_h)):
+            if pt.shape != (4 * _q64(curve),) or not g2_check(curve, pt) or not pt.any():
+                raise ValueError(f"OpenKey: {name} is not a point of order r on the twist")
+
+    @classmethod
+    def from_trapdoor(cls, curve: str, tau: int) -> "OpenKey":
+        """The key matching `plonk_synth_srs` / `SyntheticInstance(tau=...)`: beta_h = tau * H."""
+        h = g2_generator(curve)
+        return cls(curve, g1_generator(curve), h, g2_mul(curve, _fr.FIELDS[curve].to_limbs(tau % _fr.FIELDS[curve].p), h))
+
+
+def _jac(curve: str, xy: np.ndarray) -> np.ndarray:
+    n = _q64(curve)
+    one = np.array(_fq_mont(curve, 1), dtype=np.uint64)
+    if not xy.any():
+        return np.concatenate([one, one, np.zeros(n, np.uint64)])
+    return np.concatenate([xy, one])
+
+
+def _sum_points(worker, curve: str, pts: Sequence[np.ndarray]) -> np.ndarray:
+    acc = _jac(curve, np.zeros(2 * _q64(curve), np.uint64))
+    for p in pts:
+        if p.any():
+            acc = worker.g1_add(acc, _jac(curve, p))
+    xy, inf = worker.g1_to_affine(acc)
+    return np.zeros_like(xy) if inf else xy
+
+
+def _vk_state(curve: str, vk: dict, num_inputs: int) -> _ffi.VerifyKey:
+    t = PlonkTranscript(curve)
+    t.append_vk_and_pub_input(vk["domain_size"], num_inputs, list(vk["k"]), vk["selector_comms"], vk["sigma_comms"], [])
+    s = t.t.strobe
+    key = _ffi.VerifyKey()
+    key.domain_size = int(vk["domain_size"])
+    key.num_inputs = num_inputs
+    k = np.ascontiguousarray(vk["k"], dtype=np.uint64).reshape(5, 4)
+    for i in range(5):
+        for j in range(4):
+            key.k[i][j] = int(k[i, j])
+    key.transcript_state[:] = list(s.state)
+    key.transcript_pos[:] = [s.pos, s.pos_begin, s.cur_flags]
+    return key
+
+
+def proof_record(curve: str, proof: dict) -> np.ndarray:
+    """One `plonk_verify_batch_dev` record: 13 affine points in `Proof` field order, then the 10 evaluations."""
+    pts = list(proof["wires_poly_comms"]) + [proof["prod_perm_poly_comm"]] + list(proof["split_quot_poly_comms"]) \
+        + [proof["opening_proof"], proof["shifted_opening_proof"]]
+    evs = list(proof["wires_evals"]) + list(proof["wire_sigma_evals"]) + [proof["perm_next_eval"]]
+    if len(pts) != NPTS or len(evs) != NEVALS:
+        raise ValueError("proof shape: 13 commitments and 10 evaluations expected")
+    return np.concatenate([_point_xy(curve, p) for p in pts] + [np.ascontiguousarray(e, dtype=np.uint64).reshape(4) for e in evs])
+
+
+def device_verify(worker, vk: dict, public_inputs_list, proofs, rho: np.ndarray, debug: bool = False):
+    """The device part for K proofs: (points [K, 2 (rho B, rho A), 2Q] u64, status [K] u32, debug [K, 9, 4] or None)."""
+    curve = worker.curve_name
+    n64 = _q64(curve)
+    K = len(proofs)
+    if len(public_inputs_list) != K or rho.shape[0] != K:
+        raise ValueError("one public-input list and one rho per proof")
+    pis = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 4) for p in public_inputs_list]
+    num_inputs = pis[0].shape[0] if K else 0
+    if any(p.shape[0] != num_inputs for p in pis):
+        raise ValueError("every proof of a batch needs the same number of public inputs")
+    if len(vk["selector_comms"]) != 13 or len(vk["sigma_comms"]) != 5:
+        raise ValueError("verifying key shape")
+    key = _vk_state(curve, vk, num_inputs)
+    comms = np.concatenate([_point_xy(curve, c) for c in list(vk["selector_comms"]) + list(vk["sigma_comms"])])
+    recs = np.stack([proof_record(curve, p) for p in proofs]) if K else np.zeros((0, 2 * n64 * NPTS + 4 * NEVALS), np.uint64)
+    bufs = []
+    alloc = lambda nbytes: bufs.append(worker.alloc(max(nbytes, 8))) or bufs[-1]
+    try:
+        d_comms = alloc(comms.nbytes).upload(comms)
+        d_recs = alloc(recs.nbytes).upload(recs)
+        pub = np.concatenate(pis) if num_inputs else np.zeros((1, 4), np.uint64)
+        d_pub = alloc(pub.nbytes).upload(pub)
+        d_rho = alloc(rho.nbytes).upload(np.ascontiguousarray(rho, dtype=np.uint64))
+        d_out = alloc(K * 2 * 2 * n64 * 8)
+        d_status = alloc(K * 4)
+        d_dbg = alloc(K * 9 * 32) if debug else None
+        if debug:
+            worker.memset_dev(d_dbg.ptr, 0, K * 9 * 32)
+        key.d_comms = d_comms.ptr
+        _ffi.check(_lib().plonk_verify_batch_dev(worker.ctx, C.byref(key), K, d_recs.ptr, d_pub.ptr if num_inputs else None, d_rho.ptr, d_out.ptr,
+                                                 d_status.ptr, d_dbg.ptr if debug else None))
+        pts = d_out.download((K, 2, 2 * n64))
+        status = d_status.download((K,), dtype=np.uint32)
+        dbg = d_dbg.download((K, 9, 4)) if debug else None
+    finally:
+        for b in bufs:
+            b.free()
+    return pts, status, dbg
+
+
+def _rhos(curve: str, K: int, seed: Optional[int]) -> np.ndarray:
+    f = _fr.FIELDS[curve]
+    draw = (lambda: secrets.randbelow(f.p - 1) + 1) if seed is None else (lambda r=random.Random(seed): r.randrange(1, f.p))
+    return np.stack([f.to_limbs(draw()) for _ in range(K)]) if K else np.zeros((0, 4), np.uint64)
+
+
+def batch_verify(worker, vk: dict, open_key: OpenKey, public_inputs_list, proofs, seed: Optional[int] = None, stats: Optional[dict] = None,
+                 _rho: Optional[np.ndarray] = None) -> list:
+    """One verdict per proof.  `stats` (a dict, optional) receives "pairing_checks" and the status word of every proof ("status")."""
+    curve = worker.curve_name
+    if open_key.curve != curve:
+        raise ValueError("open key and worker are on different curves")
+    K = len(proofs)
+    rho = _rhos(curve, K, seed) if _rho is None else _rho
+    pts, status, _ = device_verify(worker, vk, public_inputs_list, proofs, rho)
+    verdict = [False] * K
+    checks = [0]
+
+    def holds(idx):
+        checks[0] += 1
+        b = _sum_points(worker, curve, [pts[i, 0] for i in idx])
+        a = _sum_points(worker, curve, [pts[i, 1] for i in idx])
+        return pairing_check(curve, [a, _g1_neg(curve, b)], [open_key.beta_h, open_key.h])
+
+    def bisect(idx):
+        if not idx:
+            return
+        if holds(idx):
+            for i in idx:
+                verdict[i] = True
+        elif len(idx) > 1:
+            bisect(idx[:len(idx) // 2])
+            bisect(idx[len(idx) // 2:])
+
+    bisect([i for i in range(K) if status[i] == 0])
+    if stats is not None:
+        stats["pairing_checks"] = checks[0]
+        stats["status"] = [int(s) for s in status]
+    return verdict
+
+
+def verify(worker, vk: dict, open_key: OpenKey, public_inputs, proof: dict, stats: Optional[dict] = None) -> bool:
+    """One proof, the single check of jf-plonk's verify (rho = 1)."""
+    one = _fr.FIELDS[worker.curve_name].to_limbs(1)[None, :]
+    return batch_verify(worker, vk, open_key, [public_inputs], [proof], stats=stats, _rho=one)[0]
+
+
+def check_srs(worker, open_key: OpenKey, count: int, seed: Optional[int] = None) -> bool:
+    """The resident commit key P_0..P_count is powers of the tau in open_key.beta_h:
+    e(sum rho_i P_(i+1), H) == e(sum rho_i P_i, beta H) over i < count, both sums by the resident-base MSM (plonk_msm_dev)."""
+    curve = worker.curve_name
+    f = _fr.FIELDS[curve]
+    draw = (lambda: secrets.randbelow(f.p - 1) + 1) if seed is None else (lambda r=random.Random(seed): r.randrange(1, f.p))
+    rho = np.array([[(x >> (64 * j)) & (2 ** 64 - 1) for j in range(4)] for x in (draw() for _ in range(count))], dtype=np.uint64)   # canonical
+    d = worker.alloc(max(rho.nbytes, 8)).upload(rho)
+    try:
+        s0, inf0 = worker.g1_to_affine(worker.msm_dev(0, count, d.ptr))
+        s1, inf1 = worker.g1_to_affine(worker.msm_dev(1, count + 1, d.ptr))
+    finally:
+        d.free()
+    if inf0 or inf1:
+        return False
+    s0 = s0.reshape(-1)
+    s1 = s1.reshape(-1)
+    return pairing_check(curve, [s1, _g1_neg(curve, s0)], [open_key.h, open_key.beta_h])

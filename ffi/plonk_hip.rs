@@ -48,6 +48,17 @@ pub struct plonk_msm_workload {
 }
 
 /// dispatcher2.rs:443-456 (selector order), :382-432 (the 25 coset-FFT outputs)
+/// include/plonk_hip.h plonk_verify_key: what plonk_verify_batch_dev needs of a verifying key.
+#[repr(C)]
+pub struct plonk_verify_key {
+    pub domain_size: u64,
+    pub num_inputs: u64,
+    pub k: [[u64; 4]; 5],
+    pub d_comms: *const c_void,
+    pub transcript_state: [u8; 200],
+    pub transcript_pos: [u32; 3],
+}
+
 #[repr(C)]
 pub struct plonk_quotient_inputs {
     pub selectors: [*const c_void; 13],
@@ -145,6 +156,12 @@ extern "C" {
     pub fn plonk_circuit_witness_dev(ctx: *mut plonk_ctx, d_wire_vars: *const c_void, n: usize, d_witness: *const c_void, num_vars: usize, d_wires: *mut c_void) -> c_int;
     pub fn plonk_circuit_check_dev(ctx: *mut plonk_ctx, d_wires: *const c_void, d_selector_evals: *const c_void, d_pub_input: *const c_void,
                                    d_perm_idx: *const c_void, n: usize, first_bad_gate: *mut i64, first_bad_copy: *mut i64) -> c_int;
+    pub fn plonk_g2_generator(curve: c_int, out: *mut u64) -> c_int;
+    pub fn plonk_g2_mul(curve: c_int, scalar: *const u64, input: *const u64, out: *mut u64) -> c_int;
+    pub fn plonk_g2_check(curve: c_int, pt: *const u64, ok: *mut c_int) -> c_int;
+    pub fn plonk_pairing_check(curve: c_int, k: usize, g1_xy: *const u64, g2_xy: *const u64, is_one: *mut c_int) -> c_int;
+    pub fn plonk_verify_batch_dev(ctx: *mut plonk_ctx, vk: *const plonk_verify_key, k: usize, d_proofs: *const c_void, d_pub_inputs: *const c_void,
+                                  d_rho: *const c_void, d_out_points: *mut c_void, d_status: *mut c_void, d_debug: *mut c_void) -> c_int;
     pub fn plonk_init_dev(ctx: *mut plonk_ctx, d_bases_xy: *const c_void, n_bases: usize, domain_size: usize, quot_domain_size: usize) -> c_int;
     pub fn plonk_debug_field_op(ctx: *mut plonk_ctx, field: c_int, op: c_int, a: *const u64, b: *const u64, out: *mut u64, n: usize) -> c_int;
     pub fn plonk_set_option(ctx: *mut plonk_ctx, key: *const c_char, value: i64) -> c_int;

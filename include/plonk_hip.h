@@ -342,6 +342,43 @@ int plonk_circuit_witness_dev(plonk_ctx* ctx, const void* d_wire_vars, size_t n,
  * perm_idx); an entry >= 5n returns PLONK_ERR_ARG.  Synchronises. */
 int plonk_circuit_check_dev(plonk_ctx* ctx, const void* d_wires, const void* d_selector_evals, const void* d_pub_input, const void* d_perm_idx,
                             size_t n, int64_t* first_bad_gate, int64_t* first_bad_copy);
+/* G2 and the pairing, host-only (no context, no GPU), for the verifier's last step e(A, [tau]_2) * e(-B, [1]_2) == 1 (jf-plonk's verify).
+ * G2 points lie on the sextic twist (BN254: y^2 = x^3 + 3/(9+u), BLS12-381: y^2 = x^3 + 4(1+u); Fq2 = Fq[u]/(u^2+1)) and are encoded as
+ * x.c0 || x.c1 || y.c0 || y.c1 Montgomery limbs (4Q u64), all zero = infinity; G1 points as x || y (2Q u64), (0, 0) = infinity.  Coordinates
+ * must be canonical residues on the curve (PLONK_ERR_ARG otherwise).  No element of the target group crosses the ABI. */
+int plonk_g2_generator(int curve, uint64_t* out);                     /* arkworks' G2 generator */
+int plonk_g2_mul(int curve, const uint64_t* scalar, const uint64_t* in, uint64_t* out);     /* scalar: Fr, Montgomery */
+/* *ok = 1 iff pt is a canonical point on the twist in the order-r subgroup (or infinity); a bad point is a verdict, not an error. */
+int plonk_g2_check(int curve, const uint64_t* pt, int* ok);
+/* *is_one = 1 iff prod_{i<k} e(P_i, Q_i) == 1 (optimal ate, one final exponentiation).  g1_xy: k G1 points, g2_xy: k G2 points; pairs
+ * with an infinity are skipped.  Subgroup membership of the Q_i is the caller's (plonk_g2_check). */
+int plonk_pairing_check(int curve, size_t k, const uint64_t* g1_xy, const uint64_t* g2_xy, int* is_one);
+
+/* Batched verification, the per-proof part (jf-plonk's verify / batch_verify up to the pairing), one lane per proof.  For proof j it
+ * writes rho_j*A_j and rho_j*B_j of the folded check
+ *     A = W_zeta + u W_zeta_omega,   B = zeta W_zeta + u zeta w W_zeta_omega + F + u [z] - (E + u z(zeta w)) G
+ * (F, E, the linearisation: DESIGN.md §9), so that e(sum rho A, [tau]_2) == e(sum rho B, [1]_2) accepts the batch.  The Fiat-Shamir
+ * transcript is replayed on the device from the state after the verifying-key messages (append_vk_and_pub_input with the public-input
+ * count and no inputs): its 200 bytes and pos / pos_begin / cur_flags.
+ *   d_proofs     k records, each the 13 points (wires_poly_comms[5], prod_perm_poly_comm, split_quot_poly_comms[5], opening_proof,
+ *                shifted_opening_proof: 2Q u64 each, (0, 0) = infinity) then the 10 Fr (wires_evals[5], wire_sigma_evals[4],
+ *                perm_next_eval; 4 u64 each), Montgomery
+ *   d_pub_inputs k x num_inputs Fr;  d_rho k Fr (rho = 1: the single-proof check)
+ *   d_out_points k x [rho B, rho A] affine G1 (2Q u64 each), (0, 0) for a proof whose status is not 0
+ *   d_status     k u32: 0 ok, | 1 a point off the curve, | 2 a point outside the r-subgroup (BLS12-381), | 4 zeta in the domain,
+ *                | 8 a coordinate or scalar not canonical
+ *   d_debug      NULL or k x 9 Fr: beta, gamma, alpha, zeta, v, u, PI(zeta), r(zeta), E
+ * Device pointers, ordered on the context's stream; needs no SRS.  Returns once the work is enqueued. */
+typedef struct plonk_verify_key {
+    uint64_t domain_size;           /* n, a power of two >= 2 (PLONK_ERR_DOMAIN otherwise) */
+    uint64_t num_inputs;            /* public inputs per proof, <= n */
+    uint64_t k[5][4];               /* coset separators, Fr Montgomery */
+    const void* d_comms;            /* device: the 13 selector then 5 sigma commitments, affine as the proof points */
+    uint8_t transcript_state[200];
+    uint32_t transcript_pos[3];     /* pos (< 166), pos_begin, cur_flags */
+} plonk_verify_key;
+int plonk_verify_batch_dev(plonk_ctx* ctx, const plonk_verify_key* vk, size_t k, const void* d_proofs, const void* d_pub_inputs, const void* d_rho,
+                           void* d_out_points, void* d_status, void* d_debug);
 /* Use n_bases points already in HBM (PLONK_BASES_XY) as the SRS without a host round trip; they are
  * re-encoded into the library's resident form (x || y as canonical R'-Montgomery residues in 32-bit words: 64 B / 96 B per point), the caller keeps its buffer. */
 int plonk_init_dev(plonk_ctx* ctx, const void* d_bases_xy, size_t n_bases, size_t domain_size,
