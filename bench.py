@@ -11,17 +11,21 @@ the reference prover issues per proof (/root/reference/src/dispatcher2.rs:294-69
 
 Since round 6 the HEADLINE is the proof itself: a step of the timed region = ONE real five-round proof of a satisfied 2^log_n-gate circuit
 (dispatcher2.rs:192-713: 13 commitments, 7 NTT(n), 26 NTT(8n), grand product, quotient, evaluations, openings, merlin transcript), K of them
-between barriers, the last one accepted by a verifier after the timed region; metric = constraints/sec = n / (time of one proof).  The op mix
-above, on its own seeded inputs, is measured first as `op_mix` (the headline of rounds 1-5; `--headline op-mix` times only that).
+between barriers; metric = constraints/sec = n / (time of one proof).  `--headline op-mix` times the op mix above instead (the headline of
+rounds 1-5).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 24] [--curve bn254] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 24] [--curve bn254] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: set-up, W warm-up and K timed steps, --dump-outputs, the result line.  `--full` adds everything
+else the benchmark measures and checks: the op mix on its own seeded inputs first (`op_mix`), the last timed proof handed to a verifier, the
+result checks against the oracle, the next rows and proof variants, the un-overlapped roofline, the other configurations and the CPU baseline.
 
 N == 1: everything on one GPU.  Default n = 2^24, the size BASELINE.json's metric is quoted on (it fits one
         MI355X: the 8n = 2^27 transforms ping-pong two 4 GiB buffers); `--log-n 20` is configs[1].
 N  > 1: launched by torchrun, one rank per GPU.  Same n (strong scaling): every NTT is the reference's
         2-D transform — row pass, ONE RCCL all-to-all over xGMI, column pass — and every MSM is
         index-sharded with a 96-byte all-gather + host add.
-        Reported beside `value`, never part of it: `other_scheme` (rank-local coset classes, 2 collectives per step) and
+        Reported beside `value` by --full, never part of it: `other_scheme` (rank-local coset classes, 2 collectives per step) and
         `polynomial_parallel` (SURVEY §8e's alternative: whole operations per rank, whole SRS on every rank, no data-path collective).
 Only rank 0 prints, one JSON line.  The parts live in benchlib/ (one function per leg; every leg after the headline runs in its own
 try/except and under a watchdog, so a failure there costs that leg's fields, never the line).

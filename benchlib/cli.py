@@ -19,28 +19,33 @@ def parse():
     ap.add_argument("--n-domain-only", action="store_true",
                     help="BASELINE.json configs[4] (2^28-gate BN254: 'HBM-resident witness' sizing stress): the 8n quotient domain of such a circuit "
                          "does not exist on BN254 (two-adicity 28), so only the n-domain part of the step runs - 7 iNTT(n) + 13 commitments(n)")
+    ap.add_argument("--full", action="store_true",
+                    help="run everything the benchmark measures and checks besides its headline: the op-mix step beside a proof headline, the checks "
+                         "against the oracle and the verifier, the next rows and proof variants, the un-overlapped roofline, the other schemes of an N > 1 "
+                         "run, the other configurations and the CPU baseline (the options below that select among these act only with --full).  "
+                         "Without it a run does its set-up, the W warm-up and K timed steps, --dump-outputs and the result line, nothing else")
     ap.add_argument("--headline", default="proof", choices=["proof", "op-mix"],
                     help="what the K timed steps are.  'proof' (default): K real five-round proofs of a satisfied synthetic circuit (N == 1: prover.py; N > 1: "
-                         "the coset-class prover on all ranks), verified after the timed region; the op-mix step is then measured first, as a short run of its "
-                         "own (`op_mix`).  'op-mix': K op-mix steps only (the headline of rounds 1-5; what the PMC collection profiles)")
-    ap.add_argument("--no-verify", action="store_true", help="skip the post-run result checks (`verified` becomes null)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                         "the coset-class prover on all ranks); with --full also verified after the timed region, and the op-mix step is then measured first, as a "
+                         "short run of its own (`op_mix`).  'op-mix': K op-mix steps only (the headline of rounds 1-5; what the PMC collection profiles)")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the post-run result checks (`verified` becomes null, as in a run without --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline (the oracle timed on the host cores)")
     ap.add_argument("--next-rows", default="all", choices=["all", "proof", "none"],
-                    help="the SURVEY §8f rows measured after the headline: 'all' = quotient kernel, O(n) rows, the verified proof and its same-proof "
+                    help="--full: the SURVEY §8f rows measured after the headline: 'all' = quotient kernel, O(n) rows, the verified proof and its same-proof "
                          "variants; 'proof' = the verified proof only (what the configs[1] / configs[3] sub-runs use); 'none'")
     ap.add_argument("--no-next-rows", action="store_true", help="same as --next-rows none")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default run only: skip the compact re-runs at BASELINE.json's configs[1] (2^20 BN254) and configs[3] (2^22 BLS12-381)")
-    ap.add_argument("--cpu-sample-log-n", type=int, default=20, help="cpu_baseline: log2 of the first measured sample (every op of the step once)")
+                    help="--full, default size only: skip the compact re-runs at BASELINE.json's configs[1] (2^20 BN254) and configs[3] (2^22 BLS12-381)")
+    ap.add_argument("--cpu-sample-log-n", type=int, default=20, help="--full, cpu_baseline: log2 of the first measured sample (every op of the step once)")
     ap.add_argument("--cpu-sample-log-n2", type=int, default=22,
-                    help="cpu_baseline: log2 of the second, larger measured sample (the single-threaded transforms and the commitment once each, ~25 s); "
+                    help="--full, cpu_baseline: log2 of the second, larger measured sample (the single-threaded transforms and the commitment once each, ~25 s); "
                          "the two give the fitted exponent that is reported beside the full-size measurement.  0 = one sample only")
     ap.add_argument("--cpu-full-size", default="auto", choices=["auto", "on", "off"],
-                    help="cpu_baseline: ALSO run every op of the step once at the bench size itself (2^24: ~90 s of host time, 10 GiB of host memory), so "
+                    help="--full, cpu_baseline: ALSO run every op of the step once at the bench size itself (2^24: ~90 s of host time, 10 GiB of host memory), so "
                          "that `cpu_baseline.value` is a MEASUREMENT at the GPU line's size (`extrapolated: false`) with the smaller samples kept beside it.  "
                          "'auto' = on when the host has the memory for it; 'off' = rounds 4-5's fitted extrapolation")
     ap.add_argument("--no-poly-parallel", action="store_true",
-                    help="N > 1: skip the polynomial-level-parallel leg (whole operations per rank, no data-path collective; SURVEY §8e's alternative)")
+                    help="--full, N > 1: skip the polynomial-level-parallel leg (whole operations per rank, no data-path collective; SURVEY §8e's alternative)")
     ap.add_argument("--simulate-ranks", type=int, default=0,
                     help="diagnostic: run rank 0's share of an S-rank job on ONE GPU with a stand-in for the exchange (--sim-exchange; results are "
                          "garbage, timings are one rank's compute plus device-to-device copies of the bytes it would exchange)")
@@ -50,8 +55,8 @@ def parse():
                          "the S-1 foreign blocks of an all-gather) — HBM speed, not xGMI speed, but the lanes' overlap meets a non-zero exchange and "
                          "`sim_exchange` prices the same bytes at the xGMI link rate; 'none': collectives return at once (compute only)")
     ap.add_argument("--class-prover", action="store_true",
-                    help="also time the five prover rounds with the multi-rank coset-class prover (class_prover.py) on all ranks; "
-                         "on by default for N > 1, reported under next_rows, never part of `value`")
+                    help="N = 1 with --full: also time the five prover rounds with the multi-rank coset-class prover (class_prover.py), reported under "
+                         "next_rows, never part of `value`.  N > 1 (and --simulate-ranks / --multi-path): on by default, its K proofs are the headline")
     ap.add_argument("--no-class-prover", action="store_true", help="N > 1: skip the coset-class prover leg")
     ap.add_argument("--scheme", default="reference2d", choices=["classes", "reference2d"],
                     help="N > 1: how the step's transforms are distributed.  'classes': rank s evaluates every polynomial on ITS coset "
@@ -61,7 +66,7 @@ def parse():
                          "interleave).  'reference2d' (default): every one "
                          "of the 33 transforms as the reference's 2-D distributed transform (row pass, RCCL all-to-all, column pass), the 25 forward "
                          "coset FFTs from zero-padded rows (plonk_fft1_dev_compact), two lanes so that exchanges overlap the next transform's passes.  "
-                         "The other scheme is timed after the headline and reported as `other_scheme`")
+                         "With --full the other scheme is timed after the headline and reported as `other_scheme`")
     ap.add_argument("--overlap-phases", default="auto", choices=["auto", "on", "off"],
                     help="N = 1: issue the step's transforms on their own context WHILE the 13 commitments run on the two commitment contexts, instead "
                          "of one phase after the other.  Measured as whole bench steps, same lease (profiles/r05_opening_measurements.txt): "

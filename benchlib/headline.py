@@ -181,6 +181,15 @@ def _exchange(b, kernels, phases_ms, steps=None):
                     "the slowest peer; exposed = host-clock transform phase minus the pass kernels' own time"}
 
 
+def base_line(b):
+    """rank 0: the fields of the line that no measurement sets: what is measured, in which unit and data type, on which configuration.  The
+    timed region fills in the rest (result_line: op-mix steps; promote_proof: proofs)."""
+    bn = b.args.curve == "bn254"
+    return {"metric": None, "value": None, "unit": "constraints/s", "n_gpus": b.world, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "dtype": "u32x8 Montgomery (256-bit Fr/Fq)" if bn else "u32x8 Fr / u32x12 Fq Montgomery",
+            "data": "synthetic", "config": _config(b), "verified": None}
+
+
 def result_line(b, dt, phases_ms, steps=None, warmup=None):
     """rank 0: the line as it stands when the timed op-mix region ends; the legs that follow ADD fields to it, and the proof loop — when it
     succeeds — takes the headline fields over (promote_proof).  None on the other ranks."""
@@ -194,17 +203,10 @@ def result_line(b, dt, phases_ms, steps=None, warmup=None):
         return None
     roofline, roofline_other = rooflines(b, kernels, ms_per_step, steps)
     bn = args.curve == "bn254"
-    out = {
-        "metric": f"constraints/sec (proof-equivalent MSM+NTT hot path; {'BN254' if bn else 'BLS12-381'} PLONK)",
-        "value": round(value, 1), "unit": "constraints/s", "n_gpus": b.world, "steps": steps, "warmup": warmup,
-        "ms_per_step": round(ms_per_step, 3), "phases_ms": phases_ms, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-        "dtype": "u32x8 Montgomery (256-bit Fr/Fq)" if bn else "u32x8 Fr / u32x12 Fq Montgomery",
-        "data": "synthetic",
-        "config": _config(b),
-        "roofline": roofline, "roofline_other": roofline_other,
-        "kernels": {k: {"avg_ms": round(v["avg_ms"], 4), "launches": v["launches"], "total_ms": round(v["total_ms"], 3)} for k, v in sorted(kernels.items())},
-        "cpu_baseline": None, "other_scheme": None, "verified": None, "verification": None, "next_rows": None,
-    }
+    out = dict(base_line(b),
+               metric=f"constraints/sec (proof-equivalent MSM+NTT hot path; {'BN254' if bn else 'BLS12-381'} PLONK)",
+               value=round(value, 1), steps=steps, warmup=warmup, ms_per_step=round(ms_per_step, 3), phases_ms=phases_ms,
+               roofline=roofline, roofline_other=roofline_other, kernels=_fmt_kernels(kernels))
     if b.multi and b.transport == "rccl":
         out["exchange"] = _exchange(b, kernels, phases_ms, steps)
     if b.sim:
@@ -251,14 +253,16 @@ def promote_proof(b, out, dt, rounds_ms, kernels, steps, warmup, what, overlappe
     """rank 0: the K timed proofs take the headline fields over — `value` = n / (time per verified proof), `ms_per_step` x `steps` IS the proof
     loop, `roofline` / `kernels` are the HIP-event times of the launches inside those proofs (same kernels, same launch shapes and count as the
     op-mix step: 99 pass launches per 2^24 proof) — and the op-mix step measured before them moves to `op_mix` (SURVEY §8d's per-op mix, the
-    headline of rounds 1-5, kept for continuity)."""
+    headline of rounds 1-5, kept for continuity).  `out` = base_line(b) when no op-mix step was measured (a run without --full)."""
     ms = dt / steps * 1e3
     roofline, roofline_other = rooflines(b, kernels, ms, steps, per_rank_classes=True)
-    op = {k_: out.get(k_) for k_ in ("ms_per_step", "steps", "warmup", "phases_ms", "roofline", "roofline_other", "kernels", "exchange") if k_ in out}
-    op["constraints_per_s"] = out.get("value")
-    op["what"] = "one proof-equivalent pass of the hot path on its own seeded inputs: 7 (i)NTT(n) + 25 coset-NTT(8n) + 1 coset-iNTT(8n) + 13 commitments(n) (SURVEY §8d)"
-    out["op_mix"] = op
-    out["op_mix_ms_per_step"] = op["ms_per_step"]
+    with_op_mix = "ms_per_step" in out
+    if with_op_mix:
+        op = {k_: out.get(k_) for k_ in ("ms_per_step", "steps", "warmup", "phases_ms", "roofline", "roofline_other", "kernels", "exchange") if k_ in out}
+        op["constraints_per_s"] = out.get("value")
+        op["what"] = "one proof-equivalent pass of the hot path on its own seeded inputs: 7 (i)NTT(n) + 25 coset-NTT(8n) + 1 coset-iNTT(8n) + 13 commitments(n) (SURVEY §8d)"
+        out["op_mix"] = op
+        out["op_mix_ms_per_step"] = op["ms_per_step"]
     bn = b.args.curve == "bn254"
     out.update(metric=f"constraints/sec = n / proof time (verified five-round proof, dispatcher2.rs:192-713; {'BN254' if bn else 'BLS12-381'} PLONK)",
                value=round(b.n / (dt / steps), 1), ms_per_step=round(ms, 3), steps=steps, warmup=warmup,
@@ -268,17 +272,18 @@ def promote_proof(b, out, dt, rounds_ms, kernels, steps, warmup, what, overlappe
     if isinstance(out.get("config"), dict):
         out["config"] = dict(out["config"], workload=(f"2^{b.args.log_n}-gate {b.args.curve} circuit, ONE verified five-round proof per step: 13 commit(n) + 7 NTT(n) + 26 NTT(8n) "
                                                       f"+ permutation product + quotient evaluations + 10 evaluations + 2 openings + merlin transcript"),
-                             op_mix_workload=out["config"].get("workload"))
+                             **({"op_mix_workload": out["config"].get("workload")} if with_op_mix else {}))
     if overlapped:
         for r_ in [roofline] + list(roofline_other or []):
             if r_:
                 r_["overlap_note"] = ("launch durations taken while another context's kernels shared the GPU (key coset FFTs beside rounds 1-2 / "
-                                      "commitments beside transforms): NOT comparable with an un-overlapped line — see roofline_unoverlapped")
-    if "exchange" in out:
+                                      "commitments beside transforms): NOT comparable with an un-overlapped line — see roofline_unoverlapped (--full)")
+    if b.multi and b.transport == "rccl" and not b.emulated:
         out["exchange"] = _exchange_of_proofs(b, kernels, steps)
     if b.emulated:
         out.update(metric="EMULATED DRY RUN of bench.py's control flow (tests/hostemu, no GPU): NOT a measurement", value=None, ms_per_step=None,
-                   phases_ms=None, roofline=None, roofline_other=None, kernels=None, proof_ms=None, op_mix={"emulated": True}, op_mix_ms_per_step=None)
+                   phases_ms=None, roofline=None, roofline_other=None, kernels=None, proof_ms=None, emulated=True,
+                   **({"op_mix": {"emulated": True}, "op_mix_ms_per_step": None} if with_op_mix else {}))
         out.pop("exchange", None)
 
 

@@ -384,6 +384,11 @@ class ClassProof:
     def overlapped(self):
         return self.fft_helper is not None
 
+    def close(self):
+        """a run without --full: the timed proofs are all there is (finish() closes both itself)"""
+        self.cp.close()
+        self.inst.close()
+
     def finish(self, proof_ms, rounds_ms):
         """after the timed proofs: the resident-key variant, the verifier on rank 0 -> the row under next_rows.class_prover"""
         from distributed_plonk_amd.class_prover import ClassProver

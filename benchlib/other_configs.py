@@ -55,7 +55,8 @@ def other_configs(args):
     other = []
     t_end = time.monotonic() + BUDGET_S
     for label, extra in CONFIGS:
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--bases", args.bases,
+        # --full: an entry quotes the sub-run's op-mix step, its un-overlapped roofline and the verdicts on its step and its proof
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--bases", args.bases, "--full",
                "--no-cpu-baseline", "--next-rows", "proof", "--no-other-configs"] + extra
         try:
             fallback = None

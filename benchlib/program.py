@@ -1,6 +1,7 @@
-"""The program of one bench.py run, in order: the op-mix step, the proof loop that takes the headline over, the legs that check and extend the
-line, the CPU baseline last.  One function per stage; every stage after the first measurement runs through run_leg (an exception costs the
-stage's fields, never the line) and, where a collective could hang, under the line's watchdog."""
+"""The program of one bench.py run.  Without --full: the set-up, the timed steps of the headline, --dump-outputs, the line (_plain).  With --full,
+in order: the op-mix step, the proof loop that takes the headline over, the legs that check and extend the line, the CPU baseline last.  One
+function per stage; every stage after the first measurement runs through run_leg (an exception costs the stage's fields, never the line) and,
+where a collective could hang, under the line's watchdog."""
 import os
 import sys
 
@@ -55,6 +56,53 @@ def _dump(b, out, what, arrays):
 
 
 
+def _emit(guard, rank0):
+    """the line goes out; a failed --dump-outputs then ends the run with exit code 3"""
+    guard.emit()
+    if rank0 and "error" in (guard.out.get("dump_outputs") or {}):
+        print("bench.py --dump-outputs: " + guard.out["dump_outputs"]["error"], file=sys.stderr)
+        raise SystemExit(3)
+
+
+def _plain(b, guard, proof_headline, single):
+    """A run without --full: the set-up, the W warm-up and K timed steps of the headline, --dump-outputs and the line.  Nothing else runs: no
+    op-mix step beside a proof headline, no check against the oracle or the verifier, no leg.  A failure of the timed path ends the run."""
+    args, rank0 = b.args, b.rank == 0
+    if not proof_headline:
+        dt, phases_ms = headline.timed_steps(b, guard)
+        guard.arm(None, 0)
+        out = guard.out = headline.result_line(b, dt, phases_ms)
+        _dump(b, out, "op-mix step: this rank's outputs", lambda: dump.op_mix_arrays(b, b.last_step_out))
+        if rank0:
+            out["headline"] = "op-mix step (SURVEY §8d)"
+    else:
+        if b.world > 1 or os.environ.get("PLONK_BENCH_WATCHDOG"):
+            # as around timed_steps: a proof that hangs in a collective ends the run (exit code 4) instead of hanging the driver
+            guard.start_watchdog()
+            guard.arm("headline", float(os.environ.get("PLONK_BENCH_HEADLINE_BUDGET_S", "900")))
+        if single:
+            from .legs_single import SingleProof
+            P, what, dumped = SingleProof(b), "K five-round proofs of a satisfied synthetic circuit on one GPU (prover.py; dispatcher2.rs:192-713)", "prover.py"
+        else:
+            P = M.ClassProof(b)
+            what = (f"rank 0's share of K five-round proofs by the coset-class prover on {b.sim} SIMULATED ranks (diagnostic)" if b.sim else
+                    f"K five-round proofs by the coset-class prover on all {b.world} ranks (class_prover.py; dispatcher2.rs:192-713)")
+            dumped = "class_prover.py" + (", SIMULATED ranks" if b.sim else "")
+        dt, rounds_ms, kern = headline.timed_proofs(b, guard, P, args.steps, args.warmup)
+        guard.arm(None, 0)
+        out = guard.out = headline.base_line(b) if rank0 else None
+        _dump(b, out, f"the last timed proof ({dumped})", lambda: dump.proof_arrays(P.proof))
+        if rank0:
+            headline.promote_proof(b, out, dt, rounds_ms, kern, args.steps, args.warmup,
+                                   what + "; the verifier checks the last one in a --full run", P.overlapped)
+        P.close()
+    if b.world > 1:
+        guard.emit()                             # as below: tear-down must not cost the line
+        guard.arm("teardown", 120.0)
+    b.close()
+    _emit(guard, rank0)
+
+
 def run(args, json_fd):
     from .run import Bench
     b = Bench(args)
@@ -65,14 +113,19 @@ def run(args, json_fd):
     with_class = bool((args.class_prover or multi or sim) and not args.no_class_prover and nbig)
     # The headline is the PROOF: K verified five-round proofs between barriers — the single-GPU prover at N == 1, the coset-class
     # prover on all ranks at N > 1.  The op-mix step of rounds 1-5 is measured first, as a short run of its own (`op_mix`); it is also what the line
-    # falls back to — labelled — should the proof loop fail or, on N > 1, hang in a collective (the watchdog then prints what exists).
+    # falls back to — labelled — should the proof loop fail or, on N > 1, hang in a collective (the watchdog then prints what exists).  All of that,
+    # and every leg below, with --full only: a plain run times its headline and nothing else (_plain).
     proof_headline = args.headline == "proof" and nbig > 0 and (single or (with_class and (multi or sim)))
+    if not args.full:
+        return _plain(b, guard, proof_headline, single)
     om_steps, om_warm = (min(args.steps, OPMIX_STEPS), min(args.warmup, OPMIX_WARMUP)) if proof_headline else (args.steps, args.warmup)
     dt, phases_ms = headline.timed_steps(b, guard, om_steps, om_warm)
     # ---- the result line exists from here on: everything below ADDS fields to it (or, the proof loop, takes the headline fields over), each leg in
     # its own try/except; on N > 1 (never run on more than one real GPU: gpurun grants one) also under a watchdog: should a leg hang in a
     # collective, rank 0 still prints what it has (with `aborted_optional_leg` naming the leg) and every rank exits 0.
     out = headline.result_line(b, dt, phases_ms, om_steps, om_warm)
+    if rank0:
+        out.update(cpu_baseline=None, other_scheme=None, verification=None, next_rows=None)     # the legs' fields, null until they report
     guard.arm(None, 0)
     guard.out = out
     if rank0 and args.dump_outputs:
@@ -195,9 +248,6 @@ def run(args, json_fd):
         from .cpu_baseline import cpu_baseline
         guard.start_watchdog()
         out["cpu_baseline"] = run_leg(guard, "cpu_baseline", float(os.environ.get("PLONK_BENCH_CPU_BUDGET_S", "900")), lambda: cpu_baseline(args, cfg, host_bases))
-    guard.emit()
-    if rank0 and "error" in (out.get("dump_outputs") or {}):
-        print("bench.py --dump-outputs: " + out["dump_outputs"]["error"], file=sys.stderr)
-        raise SystemExit(3)
+    _emit(guard, rank0)
 
 

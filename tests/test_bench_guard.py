@@ -200,6 +200,7 @@ def test_other_configs_fall_back_to_the_phase_after_phase_run(monkeypatch):
     assert [c[1:3] for c in calls] == [("1", None), (None, "0")] * 2
     assert all(20.0 <= c[3] <= 150.0 for c in calls) and oc.BUDGET_S <= 300
     assert all(c[0][-2:] == ["--overlap-phases", "off"] for c in calls[1::2])
+    assert all("--full" in c[0] for c in calls)              # entry_of reads the sub-run's op_mix, roofline_unoverlapped and verdicts
     # a spent budget: the first attempt gets its 20-second floor, the fall-back is refused, and the entry says so
     monkeypatch.setattr(oc, "BUDGET_S", 0.0)
     calls.clear()

@@ -1,4 +1,4 @@
-"""bench.py's N > 1 program on the one GPU a test box has: `--multi-path` runs the whole multi-rank code path — communicators, the
+"""bench.py's N > 1 program on the one GPU a test box has: `--multi-path --full` runs the whole multi-rank code path — communicators, the
 in-library RCCL collectives, two lanes of distributed transforms, sharded batched commitments, the other scheme, the polynomial-level-
 parallel leg, the verification leg — on a world of ONE rank.  Every leg that checks itself must say `true`.  (Named to sort last: a
 failure here must not keep `pytest -x` from the kernel parity tests.)"""
@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 def _run(extra):
     from conftest import free_port
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--log-n", "12", "--no-cpu-baseline", "--no-next-rows", "--no-other-configs", *extra]
+    cmd = [sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--log-n", "12", "--full", "--no-cpu-baseline", "--no-next-rows", "--no-other-configs", *extra]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout + r.stderr)[-3000:]

@@ -142,13 +142,13 @@ def test_compiled_cpp_prover_program(emu_env, tmp_path):
     check_cpp_prover(tmp_path, exe, "bls12_381", 1, 4, seed=1301, env=env)          # the six-limb Fq path of the point encodings
 
 
-def _bench_dry_run(env, world, port, extra=()):
+def _bench_dry_run(env, world, port, extra=(), full=True):
     """`bench.py --gpus N` exactly as the driver launches it (torch.distributed.run, one rank per device), against the emulation at a tiny size:
     a DRY RUN of the program's control flow.  The line it prints says `emulated`, has no value and no clock-derived field."""
     import json
     e = dict(env, HIPEMU_DEVICES="8", HIPEMU_THREADS="2", PLONK_BENCH_HEADLINE_BUDGET_S="800", PLONK_BENCH_LEG_BUDGET_S="600")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1", "--master-port", str(port),
-           "bench.py", "--gpus", str(world), "--steps", "1", "--warmup", "1", "--log-n", "9", *extra]
+           "bench.py", "--gpus", str(world), "--steps", "1", "--warmup", "1", "--log-n", "9", *(["--full"] if full else []), *extra]
     r = subprocess.run(cmd, cwd=ROOT, env=e, capture_output=True, text=True, timeout=1200)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout + r.stderr)[-3000:]
@@ -186,7 +186,7 @@ def test_bench_program_simulated_ranks(emu_env, extra):
     checked is that every leg runs and that the line says what it is (and quotes nobody else's counters)."""
     import json
     e = dict(emu_env, HIPEMU_DEVICES="4", HIPEMU_THREADS=str(min(8, os.cpu_count() or 1)))
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--log-n", "9", "--simulate-ranks", "4", *extra], cwd=ROOT, env=e,
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--log-n", "9", "--simulate-ranks", "4", "--full", *extra], cwd=ROOT, env=e,
                        capture_output=True, text=True, timeout=900)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout + r.stderr)[-3000:]
@@ -198,6 +198,16 @@ def test_bench_program_simulated_ranks(emu_env, extra):
     assert cp["simulated"] is True and cp["ranks"] == 4 and cp["rounds_1_2"].startswith("size-n iFFTs by residue class"), cp
     assert (cp["sim_exchange"]["device_bytes_out_per_proof"] > 0) and "error" not in (d.get("polynomial_parallel") or {}), d
     assert "SIMULATED ranks" in d["headline"] and "proof_headline_error" not in d, d["headline"]
+
+
+def test_bench_plain_run_multi_rank(emu_env):
+    """`bench.py --gpus 2` without --full: the class prover's K proofs on both ranks and the line — no op-mix step, no other scheme, no
+    polynomial-level-parallel leg, no verification; every rank leaves with exit code 0."""
+    from conftest import free_port
+    d = _bench_dry_run(emu_env, 2, free_port(), full=False)
+    assert d["emulated"] is True and d["value"] is None and d["n_gpus"] == 2 and d["verified"] is None
+    assert d["headline"].startswith("K five-round proofs by the coset-class prover on all 2 ranks"), d["headline"]
+    assert not set(d) & {"op_mix", "verification", "next_rows", "other_scheme", "polynomial_parallel", "roofline_unoverlapped", "aborted_optional_leg"}, sorted(d)
 
 
 def test_bench_program_multi_rank_with_phases_overlapped(emu_env):
@@ -214,14 +224,14 @@ def test_bench_program_multi_rank_with_phases_overlapped(emu_env):
 
 @pytest.mark.parametrize("overlap", ["off", "auto"])
 def test_bench_program_single_rank_line_has_every_field(emu_env, overlap):
-    """`python bench.py` as the driver runs it at N = 1 (here: 2^7 gates on the emulation): the op-mix step, its verification against the oracle, the
+    """`python bench.py --full` at N = 1 (here: 2^7 gates on the emulation): the op-mix step, its verification against the oracle, the
     proof loop that takes the headline over (round 6), the next rows and the verifier all execute, and the line carries exactly these top-level
     fields (the round-3 program's, plus `headline`, `op_mix`, `roofline_unoverlapped`; an emulated line has no clock-derived field by construction).  "off": the step as the
     2^24 line runs it, one phase after the other; "auto": at this size the transforms are issued while the commitment threads run (the
     configs[1] / configs[3] sub-runs)."""
     import json
     e = dict(emu_env, HIPEMU_DEVICES="4", HIPEMU_THREADS=str(min(8, os.cpu_count() or 1)))
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--log-n", "7", "--overlap-phases", overlap], cwd=ROOT, env=e,
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--log-n", "7", "--overlap-phases", overlap, "--full"], cwd=ROOT, env=e,
                        capture_output=True, text=True, timeout=900)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout + r.stderr)[-3000:]
@@ -245,7 +255,7 @@ def test_bench_program_proof_only_sub_run(emu_env):
     same rounds without it as a variant, which must give the same proof."""
     import json
     e = dict(emu_env, HIPEMU_DEVICES="4", HIPEMU_THREADS=str(min(8, os.cpu_count() or 1)), PLONK_BENCH_HELPER_AB="1")
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--log-n", "7", "--curve", "bls12_381", "--next-rows", "proof"], cwd=ROOT, env=e,
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "1", "--warmup", "1", "--log-n", "7", "--curve", "bls12_381", "--full", "--next-rows", "proof"], cwd=ROOT, env=e,
                        capture_output=True, text=True, timeout=900)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout + r.stderr)[-3000:]
@@ -265,7 +275,7 @@ def test_bench_dump_outputs_are_the_same_in_every_run(emu_env, tmp_path, headlin
     e = dict(emu_env, HIPEMU_DEVICES="4", HIPEMU_THREADS=str(min(8, os.cpu_count() or 1)))
     files = []
     for run in ("a", "b"):
-        r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--log-n", "7", "--headline", headline, "--no-next-rows",
+        r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--log-n", "7", "--headline", headline, "--full", "--no-next-rows",
                             "--no-cpu-baseline", "--no-other-configs", "--dump-outputs", str(tmp_path / run)], cwd=ROOT, env=e,
                            capture_output=True, text=True, timeout=900)
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -280,6 +290,36 @@ def test_bench_dump_outputs_are_the_same_in_every_run(emu_env, tmp_path, headlin
     for f in files[0]:
         a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
         assert a.dtype == np.float64 and np.array_equal(a, b), f
+
+
+@pytest.mark.parametrize("headline", ["proof", "op-mix"])
+def test_bench_plain_run_is_the_headline_alone(emu_env, tmp_path, headline):
+    """`bench.py` without --full: set-up, warm-up, the timed steps, --dump-outputs and the line — no op-mix step beside the proof, no check, no leg
+    (the line carries none of their fields) — and the arrays it dumps are those of a --full run with the same arguments."""
+    import json
+    import numpy as np
+    e = dict(emu_env, HIPEMU_DEVICES="4", HIPEMU_THREADS=str(min(8, os.cpu_count() or 1)))
+    lines = {}
+    for run, extra in (("plain", []), ("full", ["--full", "--no-next-rows", "--no-cpu-baseline", "--no-other-configs"])):
+        r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--log-n", "7", "--headline", headline, *extra,
+                            "--dump-outputs", str(tmp_path / run)], cwd=ROOT, env=e, capture_output=True, text=True, timeout=900)
+        out = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert r.returncode == 0 and len(out) == 1, (r.stdout + r.stderr)[-3000:]
+        lines[run] = json.loads(out[0])
+    d = lines["plain"]
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "steps", "warmup", "headline", "dump_outputs"} <= set(d), sorted(d)     # (no clock field: emulated)
+    assert not set(d) & {"op_mix", "verification", "prover_verified", "next_rows", "roofline_unoverlapped", "cpu_baseline", "other_configs", "other_scheme",
+                         "polynomial_parallel"}, sorted(d)
+    assert d["verified"] is None and d["steps"] == 2 and d["warmup"] == 1 and d["emulated"] is True
+    assert lines["full"]["verified"] is True and ("op_mix" in lines["full"]) == (headline == "proof")
+    for k in ("unit", "higher_is_better", "dtype", "n_gpus", "data"):
+        assert d[k] == lines["full"][k], k
+    if headline == "proof":
+        assert d["headline"].startswith("K five-round proofs") and d["config"]["workload"] == lines["full"]["config"]["workload"]
+    files = d["dump_outputs"]["files"]
+    assert files == lines["full"]["dump_outputs"]["files"] and sorted(os.listdir(tmp_path / "plain")) == files
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "plain" / f), np.load(tmp_path / "full" / f)), f
 
 
 def test_differential_fuzz_slice(emu_env):

@@ -9,7 +9,7 @@ mkdir -p $O
 cd $R
 timeout 900 python -m pytest tests -m gpu -x -q -p no:cacheprovider 2>&1 | grep -E "passed|failed|error" | tail -2 | tee $O/${TAG}_closing_gpu_suite.txt
 timeout 200 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee $O/${TAG}_closing_smoke.txt
-timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_bench_2p24_final.json 2> $O/${TAG}_closing_bench.err; echo "bench rc $?"
+timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/${TAG}_bench_2p24_final.json 2> $O/${TAG}_closing_bench.err; echo "bench rc $?"
 timeout 900 bash tools/collect_profiles.sh $TAG 2>&1 | tail -4
 python - $TAG <<'PY'
 import json, sys

@@ -3,7 +3,7 @@
 # usage (gpurun): bash tools/trace_commit_overlap.sh ["batch persist" ...]     then: python tools/trace_show.py gpurun_out/trace_b<batch>_p<persist>.tsv
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O
-COMMON="--steps 1 --warmup 1 --no-cpu-baseline --no-next-rows --no-other-configs --no-verify ${EXTRA:-}"
+COMMON="--steps 1 --warmup 1 --full --no-cpu-baseline --no-next-rows --no-other-configs --no-verify ${EXTRA:-}"
 if [ $# -eq 0 ]; then set -- "1 4"; fi
 for cfg in "$@"; do
   read b p <<< "$cfg"
