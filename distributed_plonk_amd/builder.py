@@ -1,0 +1,342 @@
+"""Building a circuit from operations, and solving its witness on the device.
+
+The reference's end-to-end test does not write selector tables: it builds its circuit with jellyfish's constraint builder
+(`PlonkCircuit::new`, `create_variable`, the arithmetic gates; generate_circuit, dispatcher2.rs:1226-1271) and the builder knows the
+witness.  `CircuitBuilder` is the array-oriented counterpart on the host: every operation takes variable ids as scalars or 1-D integer
+arrays broadcast against each other, emits one gate per element in one numpy step and returns the ids of the new variables, so a
+2^22-gate circuit is a few hundred calls.  `build()` gives a `BuiltCircuit`: exactly the arrays `circuit.Circuit` takes, padded to a
+power of two, plus `def_gate` — which gate defines each variable.  From the values of the inputs and public inputs alone
+`BuiltCircuit.solve_dev` has the device evaluate every defining gate in dependency order (plonk_circuit_solve_dev), and
+`BuiltCircuit.preprocess` continues into `circuit.preprocess_dev` without the witness leaving HBM:
+
+    b = CircuitBuilder("bn254")
+    x, y = b.input(2)
+    out = b.public_input()
+    t = b.pow5_lc([x, y], [1, 3], const=7)            # x^5 + 3 y^5 + 7
+    b.enforce_equal(b.mul(t, y), out)
+    inst = b.build().preprocess(worker, inputs, public_inputs)      # a circuit.PreprocessedCircuit
+
+Field constants are Python ints (or sequences of them, one per gate), reduced mod r.  Gate equation and selector order: circuit.py.
+"""
+from __future__ import annotations
+
+from typing import Mapping, Optional, Sequence
+
+import numpy as np
+
+from . import circuit as _circuit
+from . import fr as _fr
+from .synthetic import NUM_SELECTORS, NUM_WIRE_TYPES
+from .worker import PlonkWorker
+
+SELECTOR_INDEX = {**{f"q_lc{i}": i for i in range(4)}, "q_mul0": 4, "q_mul1": 5, **{f"q_hash{i}": 6 + i for i in range(4)}, "q_o": 10, "q_c": 11}
+GIVEN = 0xFFFFFFFF                                    # def_gate of a variable no gate defines
+_SCALARS = (int, np.integer)
+
+
+class BuiltCircuit:
+    """What CircuitBuilder.build() returns.  wire_vars (5, n) u32, selector_evals (13, n, 4) Montgomery limbs, n a power of two (jellyfish's
+    padding gates at the end); def_gate (num_vars,) u32: the gate that defines the variable, GIVEN for an input; input_vars / public_vars:
+    the ids whose values `inputs` / `public_inputs` carry, in that order; the IO gate of public_vars[i] is gate i."""
+
+    def __init__(self, curve: str, wire_vars, selector_evals, num_vars: int, def_gate, input_vars, public_vars, zero_var: int, num_gates: int):
+        self.curve, self.wire_vars, self.selector_evals, self.num_vars, self.def_gate = curve, wire_vars, selector_evals, num_vars, def_gate
+        self.input_vars, self.public_vars, self.zero_var = input_vars, public_vars, zero_var
+        self.num_public = len(public_vars)
+        self.num_gates_unpadded = num_gates
+        self._dev = None                              # (worker, [wire_vars, selector_evals, def_gate] device buffers)
+
+    @property
+    def n(self) -> int:
+        return self.wire_vars.shape[1]
+
+    @property
+    def log_n(self) -> int:
+        return self.n.bit_length() - 1
+
+    def _upload(self, worker: PlonkWorker):
+        if self._dev is not None and self._dev[0] is not worker:
+            self.close()
+        if self._dev is None:
+            bufs = []
+            try:
+                for a in (self.wire_vars, self.selector_evals, self.def_gate):
+                    bufs.append(worker.alloc(a.nbytes).upload(a))
+            except BaseException:
+                for b in bufs:
+                    b.free()
+                raise
+            self._dev = (worker, bufs)
+        return self._dev[1]
+
+    def close(self):
+        """Free the device copy of the circuit that solve_dev keeps between calls."""
+        if self._dev is not None:
+            for b in self._dev[1]:
+                b.free()
+            self._dev = None
+
+    def solve_dev(self, worker: PlonkWorker, inputs, public_inputs=None) -> "SolvedWitness":
+        """inputs: (len(input_vars), 4), public_inputs: (num_public, 4) Montgomery limbs.  The circuit is uploaded once per worker and kept
+        (close() frees it); the witness buffer gets the inputs and zero, the device fills in every defined variable.  Raises
+        circuit.UnsolvableCircuit naming the smallest variable on a dependency cycle.  -> SolvedWitness (device buffers; close() it)."""
+        if worker.curve_name != self.curve:
+            raise ValueError(f"circuit over {self.curve}, worker over {worker.curve_name}")
+        inp = np.ascontiguousarray(np.zeros((0, 4)) if inputs is None else inputs, dtype=np.uint64).reshape(-1, 4)
+        pub = np.ascontiguousarray(np.zeros((0, 4)) if public_inputs is None else public_inputs, dtype=np.uint64).reshape(-1, 4)
+        if inp.shape[0] != len(self.input_vars):
+            raise ValueError(f"{inp.shape[0]} input values for {len(self.input_vars)} inputs")
+        if pub.shape[0] != self.num_public:
+            raise ValueError(f"{pub.shape[0]} public input values for {self.num_public} public inputs")
+        d_vars, d_sel, d_def = self._upload(worker)
+        n = self.n
+        out = SolvedWitness(worker, self, d_vars.ptr, d_sel.ptr)
+        try:
+            witness = np.zeros((self.num_vars, 4), dtype=np.uint64)
+            witness[self.input_vars] = inp
+            out.d_witness.upload(witness)
+            del witness
+            worker.memset_dev(out.d_pub.ptr, 0, n * 32)
+            if self.num_public:
+                out.d_pub.upload(pub)
+            unsolved, out.levels, out.evaluations = worker.circuit_solve_dev(d_vars.ptr, n, self.num_vars, d_sel.ptr, out.d_pub.ptr, d_def.ptr,
+                                                                             out.d_witness.ptr)
+            if unsolved >= 0:
+                raise _circuit.UnsolvableCircuit(unsolved)
+        except BaseException:
+            out.close()
+            raise
+        return out
+
+    def preprocess(self, worker: PlonkWorker, inputs, public_inputs=None, check: bool = True, k: Optional[np.ndarray] = None) -> _circuit.PreprocessedCircuit:
+        """solve_dev, then circuit.preprocess_dev on the same device buffers.  check: the satisfiability kernel validates every gate, the
+        constraints included, so a wrong input raises circuit.UnsatisfiedCircuit."""
+        s = self.solve_dev(worker, inputs, public_inputs)
+        try:
+            return _circuit.preprocess_dev(worker, s.d_wire_vars, self.n, self.num_vars, s.d_witness.ptr, s.d_selector_evals, s.d_pub.ptr, self.num_public,
+                                           k, check)
+        finally:
+            s.close()
+
+    def circuit(self, worker: PlonkWorker, inputs, public_inputs=None) -> _circuit.Circuit:
+        """The same circuit as host arrays with the solved witness downloaded (small sizes, tests)."""
+        s = self.solve_dev(worker, inputs, public_inputs)
+        try:
+            return _circuit.Circuit(self.wire_vars, s.witness(), self.selector_evals, s.d_pub.download((self.num_public, 4)))
+        finally:
+            s.close()
+
+
+class SolvedWitness:
+    """Device buffers of one solve: d_witness (num_vars Fr) and d_pub (n Fr, public inputs at the IO gates), beside the pointers of the
+    circuit's own upload (owned by the BuiltCircuit).  levels / evaluations: what the solver reports."""
+
+    def __init__(self, worker: PlonkWorker, built: BuiltCircuit, d_wire_vars: int, d_selector_evals: int):
+        self.built, self.d_wire_vars, self.d_selector_evals = built, d_wire_vars, d_selector_evals
+        self.levels = self.evaluations = 0
+        self.d_witness = worker.alloc(built.num_vars * 32)
+        try:
+            self.d_pub = worker.alloc(built.n * 32)
+        except BaseException:
+            self.d_witness.free()
+            raise
+
+    def witness(self) -> np.ndarray:
+        return self.d_witness.download((self.built.num_vars, 4))
+
+    def close(self):
+        for b in (self.d_witness, self.d_pub):
+            if b.ptr:
+                b.free()
+
+
+class CircuitBuilder:
+    """Collects gates; see the module docstring.  Variable 0 is `zero`, variable 1 is `one` (each pinned by a constant gate, as jellyfish's
+    PlonkCircuit::new does); unused wires read `zero`.  A refused call (unknown id, mismatched lengths, ...) raises ValueError and emits
+    nothing."""
+
+    def __init__(self, curve: str):
+        self.curve = curve
+        self.field = _fr.FIELDS[curve]
+        self.num_vars = 0
+        self._chunks = []                             # (wires (5, k) int64, {selector index: int | list of k ints}, defines, is_io)
+        self._inputs = []
+        self._publics = []
+        self._constants = {}
+        self.zero = None
+        self.zero = self.constant(0)
+        self.one = self.constant(1)
+
+    @property
+    def num_gates(self) -> int:
+        return sum(c[0].shape[1] for c in self._chunks)
+
+    # ------------------------------------------------------------------ arguments
+    def _new_vars(self, count: int) -> np.ndarray:
+        ids = np.arange(self.num_vars, self.num_vars + count, dtype=np.int64)
+        self.num_vars += count
+        if self.num_vars > GIVEN - 1:
+            raise ValueError("more than 2^32 - 2 variables")
+        return ids
+
+    def _var(self, a) -> np.ndarray:
+        v = np.asarray(a)
+        if v.dtype.kind not in "iu" or v.ndim > 1:
+            raise ValueError(f"variable ids must be integers, scalar or 1-D (got dtype {v.dtype}, shape {v.shape})")
+        if v.size and (int(v.min()) < 0 or int(v.max()) >= self.num_vars):
+            raise ValueError(f"unknown variable id (ids lie in [0, {self.num_vars}))")
+        return v.astype(np.int64)
+
+    def _coef(self, c):
+        p = self.field.p
+        if isinstance(c, _SCALARS):
+            return int(c) % p
+        vals = [int(x) % p for x in (c.tolist() if isinstance(c, np.ndarray) else list(c))]
+        return vals
+
+    def _emit(self, wires4: Sequence, selectors: Mapping[str, object], out=None, is_io: bool = False):
+        """One gate per element of the broadcast arguments.  out None: wire 4 is a fresh variable that the gate defines."""
+        if len(wires4) != 4:
+            raise ValueError(f"{len(wires4)} input wires, a gate has 4")
+        wires = [self._var(w) for w in wires4] + ([] if out is None else [self._var(out)])
+        sel = {}
+        for name, val in selectors.items():
+            if name not in SELECTOR_INDEX:
+                raise ValueError(f"unknown selector {name!r} (one of {', '.join(SELECTOR_INDEX)})")
+            sel[SELECTOR_INDEX[name]] = self._coef(val)
+        sel.setdefault(SELECTOR_INDEX["q_o"], 1)
+        lens = [w.shape[0] for w in wires if w.ndim] + [len(v) for v in sel.values() if isinstance(v, list)]
+        k = max(lens, default=1)
+        if any(l not in (1, k) for l in lens):
+            raise ValueError(f"mismatched lengths {sorted(set(lens))}: array arguments must have one length (or length 1)")
+        scalar = not lens
+        for t, v in sel.items():
+            if isinstance(v, list):
+                sel[t] = v[0] if len(v) == 1 else v
+        if out is None:
+            q_o = sel[SELECTOR_INDEX["q_o"]]
+            if (q_o == 0) if isinstance(q_o, int) else (0 in q_o):
+                raise ValueError("a gate that defines its output needs q_o != 0")
+        wv = np.empty((NUM_WIRE_TYPES, k), dtype=np.int64)
+        for i, w in enumerate(wires):
+            wv[i] = w
+        new = None
+        if out is None:
+            new = self._new_vars(k)
+            wv[4] = new
+        self._chunks.append((wv, {t: v for t, v in sel.items() if isinstance(v, list) or v != 0}, out is None, is_io))
+        if new is None:
+            return None
+        return int(new[0]) if scalar else new
+
+    # ------------------------------------------------------------------ variables
+    def input(self, count: int = 1):
+        """`count` given variables (their values come with solve_dev's `inputs`, in order of creation) -> id, or ids for count > 1."""
+        ids = self._new_vars(count)
+        self._inputs.append(ids)
+        return int(ids[0]) if count == 1 else ids
+
+    def public_input(self, count: int = 1):
+        """`count` variables each defined by an IO gate (wire 4, q_o = 1, PI - e = 0); build() puts those gates first."""
+        z = np.full(count, self.zero, dtype=np.int64)
+        ids = self._emit([z, z, z, z], {}, is_io=True)
+        self._publics.append(ids)
+        return int(ids[0]) if count == 1 else ids
+
+    def constant(self, c: int) -> int:
+        """The variable of a gate q_c = c, q_o = 1; equal constants share one."""
+        c = int(c) % self.field.p
+        if c not in self._constants:
+            if self.zero is None:                     # the zero variable's own gate: its dead wires read itself
+                v = int(self._new_vars(1)[0])
+                self._chunks.append((np.full((NUM_WIRE_TYPES, 1), v, dtype=np.int64), {SELECTOR_INDEX["q_o"]: 1}, True, False))
+                self._constants[c] = v
+            else:
+                z = self.zero
+                self._constants[c] = self._emit([z, z, z, z], {"q_c": c})
+        return self._constants[c]
+
+    # ------------------------------------------------------------------ gates that define a variable
+    def gate(self, wires4: Sequence, selectors: Mapping[str, object], out=None):
+        """The general form: wires 0-3 and any of q_lc0..3, q_mul0..1, q_hash0..3, q_o (default 1), q_c.  Without `out` the gate defines a fresh
+        variable on wire 4, (q_c + sum q_lc w + q_mul0 ab + q_mul1 cd + sum q_hash w^5) / q_o, and returns it; with `out` (existing ids) it is a
+        constraint on them and returns None."""
+        return self._emit(wires4, selectors, out=out)
+
+    def _terms(self, vars_, coeffs, prefix: str) -> tuple:
+        vars_, coeffs = list(vars_), list(coeffs)
+        if len(vars_) > 4:
+            raise ValueError(f"{len(vars_)} terms: a gate takes at most 4")
+        if len(vars_) != len(coeffs):
+            raise ValueError(f"mismatched lengths: {len(vars_)} variables, {len(coeffs)} coefficients")
+        wires = vars_ + [self.zero] * (4 - len(vars_))
+        return wires, {f"{prefix}{i}": c for i, c in enumerate(coeffs)}
+
+    def lc(self, vars_, coeffs, const=0):
+        """sum coeff_i * w_i + const, up to 4 terms."""
+        wires, sel = self._terms(vars_, coeffs, "q_lc")
+        return self._emit(wires, {**sel, "q_c": const})
+
+    def pow5_lc(self, vars_, coeffs, const=0):
+        """sum coeff_i * w_i^5 + const, up to 4 terms: the Rescue-style q_hash gate."""
+        wires, sel = self._terms(vars_, coeffs, "q_hash")
+        return self._emit(wires, {**sel, "q_c": const})
+
+    def add(self, a, b):
+        return self._emit([a, b, self.zero, self.zero], {"q_lc0": 1, "q_lc1": 1})
+
+    def sub(self, a, b):
+        return self._emit([a, b, self.zero, self.zero], {"q_lc0": 1, "q_lc1": -1})
+
+    def mul(self, a, b):
+        return self._emit([a, b, self.zero, self.zero], {"q_mul0": 1})
+
+    def mul_add(self, a, b, c, d, q0=1, q1=1):
+        """q0 * a b + q1 * c d"""
+        return self._emit([a, b, c, d], {"q_mul0": q0, "q_mul1": q1})
+
+    # ------------------------------------------------------------------ constraints
+    def enforce_equal(self, a, b):
+        self._emit([a, b, self.zero, self.zero], {"q_lc0": 1, "q_lc1": -1, "q_o": 0}, out=self.zero)
+
+    def enforce_constant(self, a, c):
+        z = self.zero
+        self._emit([z, z, z, z], {"q_c": c}, out=a)
+
+    def enforce_bool(self, a):
+        self._emit([a, a, self.zero, self.zero], {"q_mul0": 1}, out=a)
+
+    def enforce_mul(self, a, b, c):
+        self._emit([a, b, self.zero, self.zero], {"q_mul0": 1}, out=c)
+
+    # ------------------------------------------------------------------ build
+    def _limbs(self, values) -> np.ndarray:
+        p, R = self.field.p, self.field.R
+        raw = b"".join((v * R % p).to_bytes(32, "little") for v in values)
+        return np.frombuffer(raw, dtype=np.uint64).reshape(-1, 4)
+
+    def build(self) -> BuiltCircuit:
+        chunks = [c for c in self._chunks if c[3]] + [c for c in self._chunks if not c[3]]
+        g = sum(c[0].shape[1] for c in chunks)
+        n = max(2, 1 << (g - 1).bit_length())
+        wire_vars = np.full((NUM_WIRE_TYPES, n), self.zero, dtype=np.uint32)
+        sel = np.zeros((NUM_SELECTORS, n, 4), dtype=np.uint64)
+        def_gate = np.full(self.num_vars, GIVEN, dtype=np.uint32)
+        scalar_limbs = {}
+        at = 0
+        for wv, s, defines, _ in chunks:
+            k = wv.shape[1]
+            wire_vars[:, at:at + k] = wv
+            for t, v in s.items():
+                if isinstance(v, list):
+                    sel[t, at:at + k] = self._limbs(v)
+                else:
+                    if v not in scalar_limbs:
+                        scalar_limbs[v] = self.field.to_limbs(v)
+                    sel[t, at:at + k] = scalar_limbs[v]
+            if defines:
+                def_gate[wv[4]] = np.arange(at, at + k, dtype=np.uint32)
+            at += k
+        cat = lambda parts: np.concatenate(parts).astype(np.int64) if parts else np.zeros(0, dtype=np.int64)
+        pub = cat([np.atleast_1d(np.asarray(p)) for p in self._publics])
+        return BuiltCircuit(self.curve, wire_vars, sel, self.num_vars, def_gate, cat(self._inputs), pub, int(self.zero), g)

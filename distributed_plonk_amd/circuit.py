@@ -38,6 +38,15 @@ class UnsatisfiedCircuit(ValueError):
         self.gate, self.position = gate, position
 
 
+class UnsolvableCircuit(ValueError):
+    """The witness solver could not reach every defined variable: `variable` is the smallest one left, on a dependency cycle of
+    defining gates or downstream of one."""
+
+    def __init__(self, variable: int):
+        super().__init__(f"variable {variable} cannot be solved: its defining gate waits for a variable on a dependency cycle")
+        self.variable = variable
+
+
 def _fr_array(a, shape_tail, what: str) -> np.ndarray:
     a = np.ascontiguousarray(a, dtype=np.uint64)
     if a.shape[-len(shape_tail):] != shape_tail:

@@ -241,16 +241,16 @@ __global__ void __launch_bounds__(CIRC_THREADS) circuit_witness_kernel(const uin
     if (threadIdx.x == 0 && bad != CIRC_NONE) atomicMin(first_bad, bad);
 }
 
-// q_c + PI + sum q_lc*w + q_mul0*ab + q_mul1*cd + sum q_hash*w^5 + q_ecc*abcde - q_o*e at gate j (the quotient kernel's gate term)
-__device__ __forceinline__ Fr circ_gate_value(const Fr* __restrict__ wires, const Fr* __restrict__ sel, const Fr* __restrict__ pub, uint64_t n, uint64_t j,
-                                         const FrParams& P) {
-    const Fr a = wires[j], b = wires[n + j], c = wires[2 * n + j], d = wires[3 * n + j], e = wires[4 * n + j];
+// The part of gate j's equation that does not read wire 4: q_c + PI + sum q_lc*w + q_mul0*ab + q_mul1*cd + sum q_hash*w^5 of the four
+// input values.  *abcd (if asked for) receives ab*cd, the factor of the q_ecc term.  The witness solver (solve_kernels.hpp) divides
+// this by q_o; the check below completes it.
+__device__ __forceinline__ Fr circ_gate_inputs_value(const Fr& a, const Fr& b, const Fr& c, const Fr& d, const Fr* __restrict__ sel,
+                                                const Fr* __restrict__ pub, uint64_t n, uint64_t j, const FrParams& P, Fr* abcd) {
     const Fr ab = fp_mul(a, b, P), cd = fp_mul(c, d, P);
+    if (abcd) *abcd = fp_mul(ab, cd, P);
     Fr acc = fp_add(sel[11 * n + j], pub[j], P);                                              // q_c + PI
     acc = fp_add(acc, fp_mul(sel[4 * n + j], ab, P), P);                                      // q_mul
     acc = fp_add(acc, fp_mul(sel[5 * n + j], cd, P), P);
-    acc = fp_add(acc, fp_mul(sel[12 * n + j], fp_mul(fp_mul(ab, cd, P), e, P), P), P);        // q_ecc * abcde
-    acc = fp_sub(acc, fp_mul(sel[10 * n + j], e, P), P);                                      // - q_o * e
     const auto lin_hash = [&](int t, const Fr& w) {                                          // q_lc * w + q_hash * w^5
         const Fr w2 = fp_sqr(w, P);
         acc = fp_add(acc, fp_mul(sel[t * n + j], w, P), P);
@@ -261,6 +261,16 @@ __device__ __forceinline__ Fr circ_gate_value(const Fr* __restrict__ wires, cons
     lin_hash(2, c);
     lin_hash(3, d);
     return acc;
+}
+
+// q_c + PI + sum q_lc*w + q_mul0*ab + q_mul1*cd + sum q_hash*w^5 + q_ecc*abcde - q_o*e at gate j (the quotient kernel's gate term)
+__device__ __forceinline__ Fr circ_gate_value(const Fr* __restrict__ wires, const Fr* __restrict__ sel, const Fr* __restrict__ pub, uint64_t n, uint64_t j,
+                                         const FrParams& P) {
+    const Fr a = wires[j], b = wires[n + j], c = wires[2 * n + j], d = wires[3 * n + j], e = wires[4 * n + j];
+    Fr abcd;
+    Fr acc = circ_gate_inputs_value(a, b, c, d, sel, pub, n, j, P, &abcd);
+    acc = fp_add(acc, fp_mul(sel[12 * n + j], fp_mul(abcd, e, P), P), P);                     // q_ecc * abcde
+    return fp_sub(acc, fp_mul(sel[10 * n + j], e, P), P);                                     // - q_o * e
 }
 
 // One lane per gate.  out[0]: first gate whose TurboPlonk equation fails; out[1]: first position p with wires[p] != wires[perm_idx[p]];
@@ -304,6 +314,31 @@ static inline int circ_radix_passes(uint64_t num_vars) {
     int bits = 0;
     while (bits < 32 && (num_vars - 1) >> bits) bits++;
     return bits <= 8 ? 1 : (bits + 7) / 8;
+}
+
+// The stable sort of N (key, position) pairs in `passes` 8-bit passes.  *kin: the keys (not modified unless it is keys[1], which the second
+// pass overwrites); *vin: their payloads, nullptr = each element's own position.  On return *kin / *vin address the sorted pairs, in
+// keys[(passes - 1) & 1] / vals[(passes - 1) & 1].  hist: 256 * ceil(N / 2048) words, sums: one word per 2048 of those.
+static inline int circ_radix_sort(const uint32_t** kin, const uint32_t** vin, uint64_t N, int passes, uint32_t* const keys[2], uint32_t* const vals[2],
+                                  uint32_t* hist, uint32_t* sums, hipStream_t stream) {
+    const uint32_t tiles = circ_grid_of(N, CIRC_TILE);
+    const uint64_t hist_len = (uint64_t)CIRC_DIGITS * tiles;
+    const uint32_t scan_blocks = circ_grid_of(hist_len, CIRC_TILE);
+    int rc;
+    for (int pass = 0; pass < passes; pass++) {
+        const uint32_t shift = 8 * pass;
+        uint32_t* ko = keys[pass & 1];
+        uint32_t* vo = vals[pass & 1];
+        hipLaunchKernelGGL(circuit_radix_hist_kernel, dim3(tiles), dim3(CIRC_THREADS), 0, stream, *kin, N, shift, tiles, hist);
+        hipLaunchKernelGGL(circuit_scan_reduce_kernel, dim3(scan_blocks), dim3(CIRC_THREADS), 0, stream, (const uint32_t*)hist, hist_len, sums);
+        hipLaunchKernelGGL(circuit_scan_sums_kernel, dim3(1), dim3(CIRC_THREADS), 0, stream, sums, scan_blocks);
+        hipLaunchKernelGGL(circuit_scan_apply_kernel, dim3(scan_blocks), dim3(CIRC_THREADS), 0, stream, hist, hist_len, (const uint32_t*)sums);
+        hipLaunchKernelGGL(circuit_radix_scatter_kernel, dim3(tiles), dim3(CIRC_THREADS), 0, stream, *kin, *vin, N, shift, tiles, (const uint32_t*)hist, ko, vo);
+        if ((rc = circ_launch_status("circuit_radix_sort"))) return rc;
+        *kin = ko;
+        *vin = vo;
+    }
+    return PLONK_OK;
 }
 
 // scratch layout (bytes, each piece 256-aligned): flag | 4 sort arrays of 5n u32 | hist | block sums | start[num_vars]
@@ -360,21 +395,7 @@ int circuit_permutation_run(int curve, const uint32_t* wire_vars, size_t n, size
         ProfScope ps("circuit_sort", stream);
         const uint32_t* kin = wire_vars;
         const uint32_t* vin = nullptr;
-        const int passes = circ_radix_passes(num_vars);
-        for (int pass = 0; pass < passes; pass++) {
-            const uint32_t shift = 8 * pass;
-            uint32_t* ko = keys[pass & 1];
-            uint32_t* vo = vals[pass & 1];
-            hipLaunchKernelGGL(circuit_radix_hist_kernel, dim3(L.tiles), dim3(CIRC_THREADS), 0, stream, kin, N, shift, L.tiles, hist);
-            hipLaunchKernelGGL(circuit_scan_reduce_kernel, dim3(L.scan_blocks), dim3(CIRC_THREADS), 0, stream, (const uint32_t*)hist, L.hist_len, sums);
-            hipLaunchKernelGGL(circuit_scan_sums_kernel, dim3(1), dim3(CIRC_THREADS), 0, stream, sums, L.scan_blocks);
-            hipLaunchKernelGGL(circuit_scan_apply_kernel, dim3(L.scan_blocks), dim3(CIRC_THREADS), 0, stream, hist, L.hist_len, (const uint32_t*)sums);
-            hipLaunchKernelGGL(circuit_radix_scatter_kernel, dim3(L.tiles), dim3(CIRC_THREADS), 0, stream, kin, vin, N, shift, L.tiles, (const uint32_t*)hist,
-                               ko, vo);
-            if ((rc = circ_launch_status("circuit_radix_sort"))) return rc;
-            kin = ko;
-            vin = vo;
-        }
+        if ((rc = circ_radix_sort(&kin, &vin, N, circ_radix_passes(num_vars), keys, vals, hist, sums, stream))) return rc;
         hipLaunchKernelGGL(circuit_link_heads_kernel, dim3(circ_grid_of(N, CIRC_THREADS)), dim3(CIRC_THREADS), 0, stream, kin, vin, N, start);
         hipLaunchKernelGGL(circuit_link_kernel, dim3(circ_grid_of(N, CIRC_THREADS)), dim3(CIRC_THREADS), 0, stream, kin, vin, N, (const uint32_t*)start, perm_idx);
         if ((rc = circ_launch_status("circuit_link"))) return rc;

@@ -358,6 +358,8 @@ int synth_circuit_dev(int curve, uint64_t seed, size_t n, size_t num_inputs, con
 // ---------------------------------------------------------------------------------------------- user circuits
 // preprocessing of circuits given as gate wiring (jellyfish's arithmetised form): kernels and launchers live in their own header
 #include "circuit_kernels.hpp"
+// the witness of such a circuit solved level by level from the gates that define its variables
+#include "solve_kernels.hpp"
 
 // ---------------------------------------------------------------------------------------------- batched proof verification
 // the per-proof work of jf-plonk's verify / batch_verify up to the pairing: kernels and launcher in their own header

@@ -411,6 +411,14 @@ class PlonkWorker:
         check(self.lib.plonk_circuit_check_dev(self.ctx, d_wires, d_selector_evals, d_pub_input, d_perm_idx or None, n, C.byref(gate), C.byref(copy)))
         return gate.value, copy.value
 
+    def circuit_solve_dev(self, d_wire_vars: int, n: int, num_vars: int, d_selector_evals: int, d_pub_input: int, d_def_gate: int, d_witness: int):
+        """Fill d_witness (num_vars Fr; given variables hold their values) with every variable that a gate defines (d_def_gate: u32 per variable,
+        0xFFFFFFFF = given), level by level (plonk_circuit_solve_dev) -> (unsolved_var or -1, levels, evaluations)."""
+        unsolved, levels, evals = C.c_int64(0), C.c_uint64(0), C.c_uint64(0)
+        check(self.lib.plonk_circuit_solve_dev(self.ctx, d_wire_vars, n, num_vars, d_selector_evals, d_pub_input, d_def_gate, d_witness, C.byref(unsolved),
+                                               C.byref(levels), C.byref(evals)))
+        return unsolved.value, levels.value, evals.value
+
     def field_op(self, field: int, op: int, a: np.ndarray, b: Optional[np.ndarray] = None) -> np.ndarray:
         a = _u64(a)
         b = _u64(b) if b is not None else None

@@ -156,6 +156,9 @@ extern "C" {
     pub fn plonk_circuit_witness_dev(ctx: *mut plonk_ctx, d_wire_vars: *const c_void, n: usize, d_witness: *const c_void, num_vars: usize, d_wires: *mut c_void) -> c_int;
     pub fn plonk_circuit_check_dev(ctx: *mut plonk_ctx, d_wires: *const c_void, d_selector_evals: *const c_void, d_pub_input: *const c_void,
                                    d_perm_idx: *const c_void, n: usize, first_bad_gate: *mut i64, first_bad_copy: *mut i64) -> c_int;
+    pub fn plonk_circuit_solve_dev(ctx: *mut plonk_ctx, d_wire_vars: *const c_void, n: usize, num_vars: usize, d_selector_evals: *const c_void,
+                                   d_pub_input: *const c_void, d_def_gate: *const c_void, d_witness: *mut c_void, unsolved_var: *mut i64,
+                                   levels: *mut u64, evaluations: *mut u64) -> c_int;
     pub fn plonk_g2_generator(curve: c_int, out: *mut u64) -> c_int;
     pub fn plonk_g2_mul(curve: c_int, scalar: *const u64, input: *const u64, out: *mut u64) -> c_int;
     pub fn plonk_g2_check(curve: c_int, pt: *const u64, ok: *mut c_int) -> c_int;

@@ -342,6 +342,23 @@ int plonk_circuit_witness_dev(plonk_ctx* ctx, const void* d_wire_vars, size_t n,
  * perm_idx); an entry >= 5n returns PLONK_ERR_ARG.  Synchronises. */
 int plonk_circuit_check_dev(plonk_ctx* ctx, const void* d_wires, const void* d_selector_evals, const void* d_pub_input, const void* d_perm_idx,
                             size_t n, int64_t* first_bad_gate, int64_t* first_bad_copy);
+/* The witness solved on the device: the counterpart of building a circuit with jellyfish's PlonkCircuit (create_variable, the arithmetic
+ * gates) and taking its witness, as the reference's generate_circuit / check_circuit_satisfiability do at dispatcher2.rs:1226-1271.
+ * def_gate: u32 [num_vars], the gate that defines the variable, or 0xFFFFFFFF = given.  witness: num_vars Fr, in/out: given variables
+ * hold their values on entry, every defined variable v is written with
+ *   (q_c + PI + sum q_lc*w + q_mul0*ab + q_mul1*cd + sum q_hash*w^5) / q_o   at gate def_gate[v], whose wire 4 reads v
+ * (q_o = +-1 costs no inversion).  wire_vars, selector_evals, pub_input as above; num_vars <= 2^32 - 2.  Checked on the device before any id
+ * is used as an index, PLONK_ERR_ARG naming the variable and gate otherwise: wire ids < num_vars; def_gate[v] < n; wire 4 of that gate
+ * reads v (hence no two variables claim one gate); q_o != 0 and q_ecc == 0 there.  Wire i < 4 of a gate is a dependency only where it is
+ * live (q_lc[i], q_hash[i] or q_mul[i/2] non-zero); a dead wire may read anything.  Evaluation runs level by level: level 0 is the defining
+ * gates none of whose live wires reads a defined variable, a gate joins level L+1 when the last of them was written in level L.  Every
+ * defining gate is evaluated once: O(n) work, a stable radix sort of the 4n (variable, consumer) pairs and one launch per level.
+ *   *unsolved_var  -1, or the smallest defined variable that could not be solved (a dependency cycle); the witness is then incomplete
+ *   *levels        dependency levels evaluated;   *evaluations   gate evaluations performed (= defined variables on success)
+ * All outputs are functions of the input alone.  Scratch from the context (4 x 4n u32 for the sort, 3n u32, 4 * num_vars bytes), given
+ * back by plonk_trim.  Synchronises. */
+int plonk_circuit_solve_dev(plonk_ctx* ctx, const void* d_wire_vars, size_t n, size_t num_vars, const void* d_selector_evals, const void* d_pub_input,
+                            const void* d_def_gate, void* d_witness, int64_t* unsolved_var, uint64_t* levels, uint64_t* evaluations);
 /* G2 and the pairing, host-only (no context, no GPU), for the verifier's last step e(A, [tau]_2) * e(-B, [1]_2) == 1 (jf-plonk's verify).
  * G2 points lie on the sextic twist (BN254: y^2 = x^3 + 3/(9+u), BLS12-381: y^2 = x^3 + 4(1+u); Fq2 = Fq[u]/(u^2+1)) and are encoded as
  * x.c0 || x.c1 || y.c0 || y.c1 Montgomery limbs (4Q u64), all zero = infinity; G1 points as x || y (2Q u64), (0, 0) = infinity.  Coordinates
