@@ -145,14 +145,7 @@ def derive_challenges(transcript, vk: dict, public_inputs_limbs, proof: dict) ->
     return ch
 
 
-def verify(cv: B.Curve, vk: dict, public_inputs_limbs, proof: dict, tau: int, transcript=None, challenges: dict | None = None) -> dict:
-    """vk: {"domain_size": n, "k": 5 Fr limbs, "selector_comms": 13 points, "sigma_comms": 5 points}; points are
-    (xy Montgomery limbs, is_infinity).  proof: the fields of `Proof` (dispatcher2.rs:699-710) in the same encodings.
-    public_inputs_limbs: `circuit.public_input()` (NOT padded).  Challenges come from `transcript` (fresh) or, for provers run
-    with caller-chosen challenges, from `challenges` (limbs; "u" optional).  Raises VerificationError; returns the intermediate
-    values on success."""
-    f = cv.fr
-    r = f.p
+def _checked_domain_size(vk: dict, proof: dict) -> int:
     n = int(vk["domain_size"])
     if n & (n - 1) or n < 2:
         raise VerificationError("domain size")
@@ -160,10 +153,18 @@ def verify(cv: B.Curve, vk: dict, public_inputs_limbs, proof: dict, tau: int, tr
             or len(proof["wires_evals"]) != NUM_WIRE_TYPES or len(proof["wire_sigma_evals"]) != NUM_WIRE_TYPES - 1
             or len(vk["selector_comms"]) != NUM_SELECTORS or len(vk["sigma_comms"]) != NUM_WIRE_TYPES):
         raise VerificationError("proof / key shape")
-    if challenges is None:
-        if transcript is None:
-            raise ValueError("verify needs a transcript or explicit challenges")
-        challenges = derive_challenges(transcript, vk, public_inputs_limbs, proof)
+    return n
+
+
+def folded_statement(cv: B.Curve, vk: dict, public_inputs_limbs, proof: dict, challenges: dict) -> dict:
+    """What a verifier COMPUTES from a proof, with no acceptance check and no trapdoor: PI(zeta), r(zeta), E, [r], F and the two sides
+    A, Bp of the folded pairing statement e(A, [tau]_2) = e(Bp, [1]_2).  Defined for any proof whose points are on the curve or at
+    infinity, honest or not (a forged proof has a well-defined A and Bp too: they just do not satisfy tau * A == Bp).  Raises
+    VerificationError only where the statement itself is undefined: a malformed key / proof shape, a point off the curve, zeta on the
+    evaluation domain.  `challenges`: limbs; "u" optional as in `verify`."""
+    f = cv.fr
+    r = f.p
+    n = _checked_domain_size(vk, proof)
     I = lambda l: fr_int(cv, l)
     beta, gamma, alpha, zeta, v = (I(challenges[k]) for k in ("beta", "gamma", "alpha", "zeta", "v"))
     u = I(challenges["u"]) if "u" in challenges else 0x5EED
@@ -220,21 +221,40 @@ def verify(cv: B.Curve, vk: dict, public_inputs_limbs, proof: dict, tau: int, tr
     evals = [r_zeta] + wv + sg
     F = g1_lincomb(cv, [(pow(v, j, r), Pj) for j, Pj in enumerate(polys)])
     E = sum(pow(v, j, r) * ej for j, ej in enumerate(evals)) % r
-    lhs1 = g1_lincomb(cv, [((tau - zeta) % r, W_z)])
-    rhs1 = g1_lincomb(cv, [(1, F), ((-E) % r, G)])
-    if lhs1 != rhs1:
-        raise VerificationError("opening at zeta rejected: (tau - zeta) * W_zeta != F - E*G")
     zeta_w = zeta * omega % r
-    lhs2 = g1_lincomb(cv, [((tau - zeta_w) % r, W_zw)])
-    rhs2 = g1_lincomb(cv, [(1, z_c), ((-z_w) % r, G)])
-    if lhs2 != rhs2:
-        raise VerificationError("opening at zeta*w rejected: (tau - zeta w) * W_zeta_w != [z] - z_w*G")
     # jf-plonk's single folded check, as the pairing would see it
     A = g1_lincomb(cv, [(1, W_z), (u, W_zw)])
     Bp = g1_lincomb(cv, [(zeta, W_z), (u * zeta_w % r, W_zw), (1, F), (u, z_c), ((-(E + u * z_w)) % r, G)])
-    if g1_lincomb(cv, [(tau, A)]) != Bp:
+    return dict(pi_eval=pi_z, lin_eval=r_zeta, batch_eval=E, A=A, Bp=Bp, lin_comm=D, batch_comm=F, zeta=zeta, zeta_w=zeta_w,
+                W_z=W_z, W_zw=W_zw, z_comm=z_c, z_w=z_w)
+
+
+def verify(cv: B.Curve, vk: dict, public_inputs_limbs, proof: dict, tau: int, transcript=None, challenges: dict | None = None) -> dict:
+    """vk: {"domain_size": n, "k": 5 Fr limbs, "selector_comms": 13 points, "sigma_comms": 5 points}; points are
+    (xy Montgomery limbs, is_infinity).  proof: the fields of `Proof` (dispatcher2.rs:699-710) in the same encodings.
+    public_inputs_limbs: `circuit.public_input()` (NOT padded).  Challenges come from `transcript` (fresh) or, for provers run
+    with caller-chosen challenges, from `challenges` (limbs; "u" optional).  Raises VerificationError; returns the intermediate
+    values on success.  The values are those of `folded_statement`; the three checks against tau are made here."""
+    _checked_domain_size(vk, proof)
+    if challenges is None:
+        if transcript is None:
+            raise ValueError("verify needs a transcript or explicit challenges")
+        challenges = derive_challenges(transcript, vk, public_inputs_limbs, proof)
+    s = folded_statement(cv, vk, public_inputs_limbs, proof, challenges)
+    r = cv.fr.p
+    G = (cv.gx, cv.gy)
+    lhs1 = g1_lincomb(cv, [((tau - s["zeta"]) % r, s["W_z"])])
+    rhs1 = g1_lincomb(cv, [(1, s["batch_comm"]), ((-s["batch_eval"]) % r, G)])
+    if lhs1 != rhs1:
+        raise VerificationError("opening at zeta rejected: (tau - zeta) * W_zeta != F - E*G")
+    lhs2 = g1_lincomb(cv, [((tau - s["zeta_w"]) % r, s["W_zw"])])
+    rhs2 = g1_lincomb(cv, [(1, s["z_comm"]), ((-s["z_w"]) % r, G)])
+    if lhs2 != rhs2:
+        raise VerificationError("opening at zeta*w rejected: (tau - zeta w) * W_zeta_w != [z] - z_w*G")
+    if g1_lincomb(cv, [(tau, s["A"])]) != s["Bp"]:
         raise VerificationError("folded check rejected")
-    return dict(challenges=challenges, lin_comm=D, lin_eval=r_zeta, batch_comm=F, batch_eval=E, pi_eval=pi_z)
+    return dict(challenges=challenges, lin_comm=s["lin_comm"], lin_eval=s["lin_eval"], batch_comm=s["batch_comm"], batch_eval=s["batch_eval"],
+                pi_eval=s["pi_eval"])
 
 
 def vk_by_trapdoor(cv: B.Curve, n: int, k_limbs, selectors_int, sigmas_int, tau: int) -> dict:

@@ -321,6 +321,7 @@ def test_invalid_arguments_are_reported(gpu_workers, curve, cid):
     wv[3, 9] = 100                                            # == num_vars
     dv, did, didx, dsig = w.alloc(wv.nbytes).upload(wv), w.alloc(5 * n * 32), w.alloc(5 * n * 8), w.alloc(5 * n * 32)
     dwit, dw = w.alloc(100 * 32), w.alloc(5 * n * 32)
+    dsel = w.alloc(13 * n * 32)                               # circuit_check_dev reads 13 selector vectors: a 5n buffer in their place is read past its end
     try:
         with pytest.raises(PlonkError) as e:
             w.circuit_permutation_dev(dv.ptr, n, 100, k, did.ptr, didx.ptr, dsig.ptr)
@@ -350,13 +351,13 @@ def test_invalid_arguments_are_reported(gpu_workers, curve, cid):
         bad_idx[200] = 5 * n
         didx.upload(bad_idx)
         with pytest.raises(PlonkError) as e:
-            w.circuit_check_dev(dw.ptr, did.ptr, did.ptr, didx.ptr, n)
+            w.circuit_check_dev(dw.ptr, dsel.ptr, did.ptr, didx.ptr, n)
         assert e.value.code == -1 and "perm_idx[200]" in str(e.value)
         # the context still works
         _, perm_idx, _ = run_permutation(w, wv, 101, k)
         assert np.array_equal(perm_idx, ref_perm_idx(wv))
     finally:
-        for b in (dv, did, didx, dsig, dwit, dw):
+        for b in (dv, did, didx, dsig, dwit, dw, dsel):
             b.free()
 
 
