@@ -16,6 +16,10 @@ power of two, plus `def_gate` — which gate defines each variable.  From the va
     b.enforce_equal(b.mul(t, y), out)
     inst = b.build().preprocess(worker, inputs, public_inputs)      # a circuit.PreprocessedCircuit
 
+Values that no gate equation yields — an inverse, a quotient, a fifth root, a bit — are HINTED: `inv`, `inv_or_zero`, `div`, `root5` and `bit`
+emit one gate whose selectors check the value and whose `hint_op` entry tells the device solver how to compute it from the gate's source
+wires (plonk_circuit_solve_hints_dev); `to_bits`, `range_check`, `is_zero`, `is_equal`, `select` and `less_than` are composed from them.
+
 Field constants are Python ints (or sequences of them, one per gate), reduced mod r.  Gate equation and selector order: circuit.py.
 """
 from __future__ import annotations
@@ -31,20 +35,29 @@ from .worker import PlonkWorker
 
 SELECTOR_INDEX = {**{f"q_lc{i}": i for i in range(4)}, "q_mul0": 4, "q_mul1": 5, **{f"q_hash{i}": 6 + i for i in range(4)}, "q_o": 10, "q_c": 11}
 GIVEN = 0xFFFFFFFF                                    # def_gate of a variable no gate defines
+HINT_INV, HINT_DIV, HINT_ROOT5, HINT_BIT = 1, 2, 3, 4 # hint_op opcodes (bits 0-7; bits 8-31: the argument, BIT's bit index)
+HINT_BIT_ARGS = 256                                   # BIT indices lie in [0, 256)
 _SCALARS = (int, np.integer)
 
 
 class BuiltCircuit:
     """What CircuitBuilder.build() returns.  wire_vars (5, n) u32, selector_evals (13, n, 4) Montgomery limbs, n a power of two (jellyfish's
     padding gates at the end); def_gate (num_vars,) u32: the gate that defines the variable, GIVEN for an input; input_vars / public_vars:
-    the ids whose values `inputs` / `public_inputs` carry, in that order; the IO gate of public_vars[i] is gate i."""
+    the ids whose values `inputs` / `public_inputs` carry, in that order; the IO gate of public_vars[i] is gate i.  hint_op (n,) u32 or None:
+    opcode | argument << 8 per gate, 0 for an ordinary gate (see HINT_*); None stands for all zero."""
 
-    def __init__(self, curve: str, wire_vars, selector_evals, num_vars: int, def_gate, input_vars, public_vars, zero_var: int, num_gates: int):
+    def __init__(self, curve: str, wire_vars, selector_evals, num_vars: int, def_gate, input_vars, public_vars, zero_var: int, num_gates: int, *,
+                 hint_op=None):
         self.curve, self.wire_vars, self.selector_evals, self.num_vars, self.def_gate = curve, wire_vars, selector_evals, num_vars, def_gate
         self.input_vars, self.public_vars, self.zero_var = input_vars, public_vars, zero_var
         self.num_public = len(public_vars)
         self.num_gates_unpadded = num_gates
-        self._dev = None                              # (worker, [wire_vars, selector_evals, def_gate] device buffers)
+        if hint_op is None:
+            hint_op = np.zeros(wire_vars.shape[1], dtype=np.uint32)
+        self.hint_op = np.ascontiguousarray(hint_op, dtype=np.uint32)
+        if self.hint_op.shape != (wire_vars.shape[1],):
+            raise ValueError(f"hint_op of shape {self.hint_op.shape} for {wire_vars.shape[1]} gates")
+        self._dev = None                              # (worker, [wire_vars, selector_evals, def_gate(, hint_op)] device buffers)
 
     @property
     def n(self) -> int:
@@ -54,13 +67,18 @@ class BuiltCircuit:
     def log_n(self) -> int:
         return self.n.bit_length() - 1
 
+    @property
+    def has_hints(self) -> bool:
+        """whether solve_dev goes through plonk_circuit_solve_hints_dev (some hint_op entry is non-zero) or plonk_circuit_solve_dev"""
+        return bool(self.hint_op.any())
+
     def _upload(self, worker: PlonkWorker):
         if self._dev is not None and self._dev[0] is not worker:
             self.close()
         if self._dev is None:
             bufs = []
             try:
-                for a in (self.wire_vars, self.selector_evals, self.def_gate):
+                for a in (self.wire_vars, self.selector_evals, self.def_gate) + ((self.hint_op,) if self.has_hints else ()):
                     bufs.append(worker.alloc(a.nbytes).upload(a))
             except BaseException:
                 for b in bufs:
@@ -88,7 +106,7 @@ class BuiltCircuit:
             raise ValueError(f"{inp.shape[0]} input values for {len(self.input_vars)} inputs")
         if pub.shape[0] != self.num_public:
             raise ValueError(f"{pub.shape[0]} public input values for {self.num_public} public inputs")
-        d_vars, d_sel, d_def = self._upload(worker)
+        d_vars, d_sel, d_def, *d_hint = self._upload(worker)
         n = self.n
         out = SolvedWitness(worker, self, d_vars.ptr, d_sel.ptr)
         try:
@@ -99,8 +117,12 @@ class BuiltCircuit:
             worker.memset_dev(out.d_pub.ptr, 0, n * 32)
             if self.num_public:
                 out.d_pub.upload(pub)
-            unsolved, out.levels, out.evaluations = worker.circuit_solve_dev(d_vars.ptr, n, self.num_vars, d_sel.ptr, out.d_pub.ptr, d_def.ptr,
-                                                                             out.d_witness.ptr)
+            if d_hint:
+                unsolved, out.levels, out.evaluations = worker.circuit_solve_hints_dev(d_vars.ptr, n, self.num_vars, d_sel.ptr, out.d_pub.ptr, d_def.ptr,
+                                                                                       d_hint[0].ptr, out.d_witness.ptr)
+            else:
+                unsolved, out.levels, out.evaluations = worker.circuit_solve_dev(d_vars.ptr, n, self.num_vars, d_sel.ptr, out.d_pub.ptr, d_def.ptr,
+                                                                                 out.d_witness.ptr)
             if unsolved >= 0:
                 raise _circuit.UnsolvableCircuit(unsolved)
         except BaseException:
@@ -159,7 +181,7 @@ class CircuitBuilder:
         self.curve = curve
         self.field = _fr.FIELDS[curve]
         self.num_vars = 0
-        self._chunks = []                             # (wires (5, k) int64, {selector index: int | list of k ints}, defines, is_io)
+        self._chunks = []                             # (wires (5, k) int64, {selector index: int | list of k ints}, defines, is_io[, hint_op (k,) u32])
         self._inputs = []
         self._publics = []
         self._constants = {}
@@ -295,6 +317,113 @@ class CircuitBuilder:
         """q0 * a b + q1 * c d"""
         return self._emit([a, b, c, d], {"q_mul0": q0, "q_mul1": q1})
 
+    # ------------------------------------------------------------------ hinted variables
+    def _hint(self, wires4, selectors, op: int, arg=0):
+        """One hint gate per element: [w0, w1, s0, s1 | y] with q_o = 0, y fresh and computed by the solver from s0, s1 (hint_op = op | arg << 8).
+        None among wires 0-1 stands for y itself."""
+        ws = [None if w is None else self._var(w) for w in wires4]
+        a = np.asarray(arg)
+        if a.dtype.kind not in "iu" or a.ndim > 1:
+            raise ValueError("a bit index must be an integer, scalar or 1-D")
+        if a.size and (int(a.min()) < 0 or int(a.max()) >= HINT_BIT_ARGS):
+            raise ValueError(f"bit index outside [0, {HINT_BIT_ARGS})")
+        lens = [w.shape[0] for w in ws if w is not None and w.ndim] + ([a.shape[0]] if a.ndim else [])
+        k = max(lens, default=1)
+        if any(l not in (1, k) for l in lens):
+            raise ValueError(f"mismatched lengths {sorted(set(lens))}: array arguments must have one length (or length 1)")
+        sel = {SELECTOR_INDEX[name]: self._coef(val) for name, val in selectors.items()}
+        new = self._new_vars(k)
+        wv = np.empty((NUM_WIRE_TYPES, k), dtype=np.int64)
+        for i, w in enumerate(ws):
+            wv[i] = new if w is None else w
+        wv[4] = new
+        hint = (np.uint32(op) | (np.broadcast_to(a, (k,)).astype(np.uint32) << np.uint32(8))).astype(np.uint32)
+        self._chunks.append((wv, {t: v for t, v in sel.items() if v != 0}, True, False, hint))
+        return new if lens else int(new[0])
+
+    def inv(self, x):
+        """y = 1 / x, checked by x * y = 1: x = 0 leaves the circuit unsatisfied (the solver then writes y = 0)."""
+        return self._hint([x, None, x, self.zero], {"q_mul0": 1, "q_c": -1}, HINT_INV)
+
+    def inv_or_zero(self, x):
+        """y = 1 / x, or 0 for x = 0, with NO constraint of its own: the caller constrains y (is_zero does)."""
+        return self._hint([self.zero, self.zero, x, self.zero], {}, HINT_INV)
+
+    def div(self, a, b):
+        """y = a / b, checked by y * b = a.  b = 0: y = 0, satisfied only for a = 0."""
+        return self._hint([None, b, a, b], {"q_mul0": 1, "q_lc2": -1}, HINT_DIV)
+
+    def root5(self, x):
+        """y = x^(1/5), checked by y^5 = x: the inverse S-box of a Rescue round in one gate (x -> x^5 is a bijection of the field)."""
+        return self._hint([None, self.zero, x, self.zero], {"q_hash0": 1, "q_lc2": -1}, HINT_ROOT5)
+
+    def bit(self, x, k):
+        """y = bit k (scalar or per element, < 256) of the canonical residue of x, checked by y * y = y.  That y is THE bit of x is up to the
+        caller's recomposition (to_bits)."""
+        return self._hint([None, None, x, self.zero], {"q_mul0": 1, "q_lc0": -1}, HINT_BIT, k)
+
+    def _nbits(self, nbits, most: int) -> int:
+        if not isinstance(nbits, _SCALARS) or not 1 <= int(nbits) <= most:
+            raise ValueError(f"nbits = {nbits!r}: an integer in 1 .. {most} (the field has {self.field.p.bit_length()} bits)")
+        return int(nbits)
+
+    def to_bits(self, x, nbits: int):
+        """The nbits low bits of x, LSB first, as a list of id arrays, with x = sum 2^i bit_i enforced: nbits bit gates and a chain of 4-term
+        lc gates from the top bits down, the last one a constraint on x — at most nbits + ceil(nbits / 3) + 1 gates per element.
+        nbits in 1 .. bit_length(r) - 1 (beyond that the decomposition is not unique).  Unsatisfied for x >= 2^nbits."""
+        nbits = self._nbits(nbits, self.field.p.bit_length() - 1)
+        x = self._var(x)
+        bits = [self.bit(x, k) for k in range(nbits)]
+        # Horner from the top: acc <- 2^j acc + (the next j bits), 3 bits per gate; the last gate has x on wire 4
+        acc, at = None, nbits
+        while True:
+            take = min(3 if acc is not None else 4, at)
+            final = at - take == 0
+            terms = bits[at - take:at]
+            wires = ([acc] if acc is not None else []) + terms
+            coeffs = ([1 << take] if acc is not None else []) + [1 << i for i in range(take)]
+            at -= take
+            if final:
+                w, sel = self._terms(wires, coeffs, "q_lc")
+                self._emit(w, sel, out=x)
+                return bits
+            acc = self.lc(wires, coeffs)
+
+    def range_check(self, x, nbits: int):
+        """x < 2^nbits (nbits as in to_bits)"""
+        self.to_bits(x, nbits)
+
+    def is_zero(self, x):
+        """b = 1 if x = 0 else 0: y = inv_or_zero(x), b = 1 - x y, and x b = 0 enforced (3 gates)."""
+        x = self._var(x)
+        y = self.inv_or_zero(x)
+        b = self._emit([x, y, self.zero, self.zero], {"q_mul0": -1, "q_c": 1})
+        self._emit([x, b, self.zero, self.zero], {"q_mul0": 1}, out=self.zero)
+        return b
+
+    def is_equal(self, a, b):
+        """1 if a = b else 0"""
+        return self.is_zero(self.sub(a, b))
+
+    def select(self, c, a, b):
+        """b + c (a - b): a where c = 1, b where c = 0.  The caller makes c boolean."""
+        c, a, b = self._var(c), self._var(a), self._var(b)
+        return self._emit([c, a, c, b], {"q_mul0": 1, "q_mul1": -1, "q_lc3": 1})
+
+    def less_than(self, a, b, nbits: int):
+        """1 if a < b else 0, for a, b < 2^nbits (both range-checked here), nbits in 1 .. bit_length(r) - 2: a - b + 2^nbits lies in
+        (0, 2^(nbits+1)), and its bit `nbits` is set exactly when a >= b."""
+        nbits = self._nbits(nbits, self.field.p.bit_length() - 2)
+        a, b = self._var(a), self._var(b)
+        lens = {w.shape[0] for w in (a, b) if w.ndim}
+        if len(lens - {1}) > 1:
+            raise ValueError(f"mismatched lengths {sorted(lens)}: array arguments must have one length (or length 1)")
+        self.range_check(a, nbits)
+        self.range_check(b, nbits)
+        d = self.lc([a, b], [1, -1], const=1 << nbits)
+        top = self.to_bits(d, nbits + 1)[nbits]
+        return self.lc([top], [-1], const=1)
+
     # ------------------------------------------------------------------ constraints
     def enforce_equal(self, a, b):
         self._emit([a, b, self.zero, self.zero], {"q_lc0": 1, "q_lc1": -1, "q_o": 0}, out=self.zero)
@@ -322,10 +451,13 @@ class CircuitBuilder:
         wire_vars = np.full((NUM_WIRE_TYPES, n), self.zero, dtype=np.uint32)
         sel = np.zeros((NUM_SELECTORS, n, 4), dtype=np.uint64)
         def_gate = np.full(self.num_vars, GIVEN, dtype=np.uint32)
+        hint_op = np.zeros(n, dtype=np.uint32)
         scalar_limbs = {}
         at = 0
-        for wv, s, defines, _ in chunks:
+        for wv, s, defines, _, *hint in chunks:
             k = wv.shape[1]
+            if hint:
+                hint_op[at:at + k] = hint[0]
             wire_vars[:, at:at + k] = wv
             for t, v in s.items():
                 if isinstance(v, list):
@@ -339,4 +471,4 @@ class CircuitBuilder:
             at += k
         cat = lambda parts: np.concatenate(parts).astype(np.int64) if parts else np.zeros(0, dtype=np.int64)
         pub = cat([np.atleast_1d(np.asarray(p)) for p in self._publics])
-        return BuiltCircuit(self.curve, wire_vars, sel, self.num_vars, def_gate, cat(self._inputs), pub, int(self.zero), g)
+        return BuiltCircuit(self.curve, wire_vars, sel, self.num_vars, def_gate, cat(self._inputs), pub, int(self.zero), g, hint_op=hint_op)

@@ -1248,18 +1248,31 @@ extern "C" int plonk_circuit_check_dev(plonk_ctx* ctx, const void* d_wires, cons
     return circuit_check_run(ctx->curve, (const Fr*)d_wires, (const Fr*)d_selector_evals, (const Fr*)d_pub_input, (const uint64_t*)d_perm_idx, n,
                              first_bad_gate, first_bad_copy, ctx->d_scratch2, ctx->stream);
 }
-extern "C" int plonk_circuit_solve_dev(plonk_ctx* ctx, const void* d_wire_vars, size_t n, size_t num_vars, const void* d_selector_evals, const void* d_pub_input,
-                                       const void* d_def_gate, void* d_witness, int64_t* unsolved_var, uint64_t* levels, uint64_t* evaluations) {
+static int circuit_solve_entry(plonk_ctx* ctx, const void* d_wire_vars, size_t n, size_t num_vars, const void* d_selector_evals, const void* d_pub_input,
+                               const void* d_def_gate, const void* d_hint_op, void* d_witness, int64_t* unsolved_var, uint64_t* levels, uint64_t* evaluations,
+                               const char* who) {
     CHECK_CTX(ctx);
     if (!d_wire_vars || !d_selector_evals || !d_pub_input || !d_def_gate || !d_witness || !unsolved_var || !levels || !evaluations)
-        return plonk_fail(PLONK_ERR_ARG, "plonk_circuit_solve_dev: null");
-    int rc = circuit_domain(ctx, n, "plonk_circuit_solve_dev", nullptr);
+        return plonk_fail(PLONK_ERR_ARG, "%s: null", who);
+    int rc = circuit_domain(ctx, n, who, nullptr);
     if (rc) return rc;
     if (num_vars == 0 || num_vars > 0xFFFFFFFEull)
-        return plonk_fail(PLONK_ERR_ARG, "plonk_circuit_solve_dev: num_vars = %zu (ids are u32 with one sentinel: 1 .. 2^32 - 2)", num_vars);
-    if ((rc = ensure_scratch2(ctx, circuit_solve_scratch_bytes(n, num_vars)))) return rc;
+        return plonk_fail(PLONK_ERR_ARG, "%s: num_vars = %zu (ids are u32 with one sentinel: 1 .. 2^32 - 2)", who, num_vars);
+    if ((rc = ensure_scratch2(ctx, circuit_solve_scratch_bytes(n, num_vars, d_hint_op != nullptr)))) return rc;
     return circuit_solve_run(ctx->curve, (const uint32_t*)d_wire_vars, n, num_vars, (const Fr*)d_selector_evals, (const Fr*)d_pub_input,
-                             (const uint32_t*)d_def_gate, (Fr*)d_witness, unsolved_var, levels, evaluations, ctx->d_scratch2, ctx->stream);
+                             (const uint32_t*)d_def_gate, (const uint32_t*)d_hint_op, (Fr*)d_witness, unsolved_var, levels, evaluations, ctx->d_scratch2,
+                             ctx->stream, who);
+}
+extern "C" int plonk_circuit_solve_dev(plonk_ctx* ctx, const void* d_wire_vars, size_t n, size_t num_vars, const void* d_selector_evals, const void* d_pub_input,
+                                       const void* d_def_gate, void* d_witness, int64_t* unsolved_var, uint64_t* levels, uint64_t* evaluations) {
+    return circuit_solve_entry(ctx, d_wire_vars, n, num_vars, d_selector_evals, d_pub_input, d_def_gate, nullptr, d_witness, unsolved_var, levels, evaluations,
+                               "plonk_circuit_solve_dev");
+}
+extern "C" int plonk_circuit_solve_hints_dev(plonk_ctx* ctx, const void* d_wire_vars, size_t n, size_t num_vars, const void* d_selector_evals,
+                                             const void* d_pub_input, const void* d_def_gate, const void* d_hint_op, void* d_witness, int64_t* unsolved_var,
+                                             uint64_t* levels, uint64_t* evaluations) {
+    return circuit_solve_entry(ctx, d_wire_vars, n, num_vars, d_selector_evals, d_pub_input, d_def_gate, d_hint_op, d_witness, unsolved_var, levels, evaluations,
+                               "plonk_circuit_solve_hints_dev");
 }
 extern "C" int plonk_debug_field_op(plonk_ctx* ctx, int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
     CHECK_CTX(ctx);

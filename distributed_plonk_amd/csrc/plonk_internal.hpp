@@ -233,9 +233,11 @@ int circuit_witness_run(const uint32_t* wire_vars, size_t n, const Fr* witness, 
 int circuit_check_run(int curve, const Fr* wires, const Fr* sel, const Fr* pub, const uint64_t* perm_idx, size_t n, int64_t* first_bad_gate,
                       int64_t* first_bad_copy, void* scratch, hipStream_t stream);
 // the witness solver (solve_kernels.hpp, built in synth.hip).  scratch: circuit_solve_scratch_bytes.
-size_t circuit_solve_scratch_bytes(size_t n, size_t num_vars);
-int circuit_solve_run(int curve, const uint32_t* wire_vars, size_t n, size_t num_vars, const Fr* sel, const Fr* pub, const uint32_t* def_gate, Fr* witness,
-                      int64_t* unsolved_var, uint64_t* levels, uint64_t* evaluations, void* scratch, hipStream_t stream);
+// hint_op: u32 per gate or NULL (solve_hints.hpp); who: the entry point named in error texts.
+size_t circuit_solve_scratch_bytes(size_t n, size_t num_vars, bool hints);
+int circuit_solve_run(int curve, const uint32_t* wire_vars, size_t n, size_t num_vars, const Fr* sel, const Fr* pub, const uint32_t* def_gate,
+                      const uint32_t* hint_op, Fr* witness, int64_t* unsolved_var, uint64_t* levels, uint64_t* evaluations, void* scratch, hipStream_t stream,
+                      const char* who);
 
 // ----------------------------------------------------------------------------------------------- O(n) prover steps (poly_ops.hip, quotient.hip)
 int quotient_evals_run(NttTables& T, const plonk_quotient_inputs* in, size_t n, size_t m, const uint64_t* alpha, const uint64_t* beta,

@@ -15,6 +15,17 @@
 // Each defining gate is evaluated exactly once; the work is O(n) plus a launch and a 8-byte read per level.  Which lane appends first
 // varies, the frontier's order with it — no output depends on that order: the witness, the number of levels and of evaluations, and
 // the smallest unsolved variable (a dependency cycle; min-reduced as in the check kernel) are functions of the input alone.
+//
+// With a hint_op array (plonk_circuit_solve_hints_dev; solve_hints.hpp) a gate may instead define its variable by a HINT — an inverse, a
+// quotient, a fifth root or a bit of the values on its wires 2 and 3, its live wires then being those sources alone — and the level loop
+// runs over THREE lists per level, one per class of cost: gates and BIT hints, INV / DIV hints (x^(r-2)), ROOT5 hints (x^d), each class
+// with a launch of its own, all three releasing consumers into the three lists of the next level by the gate's class (kept in its state
+// word), whose sizes the host reads in one 24-byte copy.  The determinism argument holds for the three-list loop as it does for one list:
+// a gate enters the list of its own class exactly once, in the level after the last of its sources was written, whichever lane
+// decrements last; its value depends on source VALUES only, and those were written by earlier levels (the launches of one level write
+// distinct variables and read none of them); levels counts iterations of the loop — dependency levels, not launches — and evaluations
+// the list entries.  So order within a list, and which of a level's launches runs first, reach no output.  Without hint_op (NULL, and
+// plonk_circuit_solve_dev) the kernels, launches and reads are the ones described above, untouched.
 #pragma once
 #include "circuit_kernels.hpp"
 
@@ -25,7 +36,9 @@ constexpr uint32_t SOLVE_DEF = 1u << 8;            // state bit 8: the gate defi
 
 // words of the flag area
 enum { SOLVE_F_BAD_ID = 0, SOLVE_F_BAD_GATE, SOLVE_F_BAD_WIRE4, SOLVE_F_BAD_QO, SOLVE_F_BAD_QECC, SOLVE_F_DEFINED, SOLVE_F_UNSOLVED, SOLVE_F_COUNT0,
-       SOLVE_F_COUNT1, SOLVE_F_WORDS };
+       SOLVE_F_COUNT1, SOLVE_F_WORDS,
+       // with hints (solve_hints.hpp): three more minima, then the frontier sizes as 2 x 3 words (parity, class) instead of COUNT0 / COUNT1
+       SOLVE_F_BAD_OP = SOLVE_F_WORDS, SOLVE_F_BAD_ARG, SOLVE_F_STRAY, SOLVE_F_HCOUNT, SOLVE_F_HINT_WORDS = SOLVE_F_HCOUNT + 6 };
 
 // One lane per variable (a tile of 2048 per workgroup).  A valid definition marks its gate; flags: the smallest offending variable per
 // kind of failure, and the number of valid definitions.
@@ -149,30 +162,36 @@ __global__ void __launch_bounds__(CIRC_THREADS) solve_unsolved_kernel(const uint
     if (threadIdx.x == 0 && bad != CIRC_NONE) atomicMin(first, bad);
 }
 
+#include "solve_hints.hpp"
+
 // scratch layout (bytes, each piece 256-aligned): flags | 4 sort arrays of 4n u32 | hist | block sums | start[num_vars] | state[n] | 2 frontiers of n u32
+// (with hints: 2 frontiers of 3 lists of n u32, one list per class)
 struct SolveScratch {
     size_t keys[2] = {0, 0}, vals[2] = {0, 0}, hist = 0, sums = 0, start = 0, state = 0, frontier[2] = {0, 0}, total = 0;
     uint64_t count = 0;
-    SolveScratch(size_t n, size_t num_vars) {
+    SolveScratch(size_t n, size_t num_vars, bool hints) {
         auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
         count = 4 * (uint64_t)n;
         const uint64_t hist_len = (uint64_t)CIRC_DIGITS * circ_grid_of(count, CIRC_TILE);
-        size_t at = al(SOLVE_F_WORDS * sizeof(unsigned long long));
+        size_t at = al(SOLVE_F_HINT_WORDS * sizeof(unsigned long long));
         for (int b = 0; b < 2; b++) { keys[b] = at; at += al(count * 4); vals[b] = at; at += al(count * 4); }
         hist = at; at += al(hist_len * 4);
         sums = at; at += al((size_t)circ_grid_of(hist_len, CIRC_TILE) * 4);
         start = at; at += al(num_vars * 4);
         state = at; at += al(n * 4);
-        for (int b = 0; b < 2; b++) { frontier[b] = at; at += al(n * 4); }
+        for (int b = 0; b < 2; b++) { frontier[b] = at; at += al((hints ? SOLVE_CLASSES : 1) * n * 4); }
         total = at;
     }
 };
 
-size_t circuit_solve_scratch_bytes(size_t n, size_t num_vars) { return SolveScratch(n, num_vars).total; }
+size_t circuit_solve_scratch_bytes(size_t n, size_t num_vars, bool hints) { return SolveScratch(n, num_vars, hints).total; }
 
-int circuit_solve_run(int curve, const uint32_t* wire_vars, size_t n, size_t num_vars, const Fr* sel, const Fr* pub, const uint32_t* def_gate, Fr* witness,
-                      int64_t* unsolved_var, uint64_t* levels, uint64_t* evaluations, void* scratch, hipStream_t stream) {
-    const SolveScratch L(n, num_vars);
+// hint_op NULL: the hint-free solver, kernel for kernel what it was before hints existed.  who: the entry point named in error texts.
+int circuit_solve_run(int curve, const uint32_t* wire_vars, size_t n, size_t num_vars, const Fr* sel, const Fr* pub, const uint32_t* def_gate,
+                      const uint32_t* hint_op, Fr* witness, int64_t* unsolved_var, uint64_t* levels, uint64_t* evaluations, void* scratch, hipStream_t stream,
+                      const char* who) {
+    const bool hints = hint_op != nullptr;
+    const SolveScratch L(n, num_vars, hints);
     char* base = (char*)scratch;
     unsigned long long* d_flags = (unsigned long long*)base;
     uint32_t* keys[2] = {(uint32_t*)(base + L.keys[0]), (uint32_t*)(base + L.keys[1])};
@@ -186,7 +205,10 @@ int circuit_solve_run(int curve, const uint32_t* wire_vars, size_t n, size_t num
     const uint32_t sentinel = (uint32_t)num_vars;        // num_vars <= 2^32 - 2: larger than every id, and not SOLVE_NONE
     const FrParams& P = fr_params(curve);
     const uint32_t var_tiles = circ_grid_of(num_vars, CIRC_TILE);
-    unsigned long long h[SOLVE_F_WORDS];
+    unsigned long long h[SOLVE_F_HINT_WORDS];
+    const size_t flag_words = hints ? SOLVE_F_HINT_WORDS : SOLVE_F_WORDS;
+    SolveExponent e_inv, e_root5;
+    if (hints && !solve_exponents(P, &e_inv, &e_root5)) return plonk_fail(PLONK_ERR_ARG, "%s: 5 divides r - 1, ROOT5 is not defined on this field", who);
     int rc;
     *unsolved_var = -1;
     *levels = 0;
@@ -194,24 +216,35 @@ int circuit_solve_run(int curve, const uint32_t* wire_vars, size_t n, size_t num
     {
         ProfScope ps("solve_setup", stream);
         // flags: the minima start at all-ones, the three counters at zero
-        HIP_TRY(hipMemsetAsync(d_flags, 0xFF, SOLVE_F_WORDS * sizeof(*d_flags), stream));
+        HIP_TRY(hipMemsetAsync(d_flags, 0xFF, flag_words * sizeof(*d_flags), stream));
         HIP_TRY(hipMemsetAsync(d_flags + SOLVE_F_DEFINED, 0, sizeof(*d_flags), stream));
-        HIP_TRY(hipMemsetAsync(d_flags + SOLVE_F_COUNT0, 0, 2 * sizeof(*d_flags), stream));
+        if (hints) HIP_TRY(hipMemsetAsync(d_flags + SOLVE_F_HCOUNT, 0, 6 * sizeof(*d_flags), stream));
+        else HIP_TRY(hipMemsetAsync(d_flags + SOLVE_F_COUNT0, 0, 2 * sizeof(*d_flags), stream));
         HIP_TRY(hipMemsetAsync(state, 0, n * 4, stream));
         hipLaunchKernelGGL(circuit_ids_check_kernel, dim3(circ_grid_of(5 * (uint64_t)n, CIRC_TILE)), dim3(CIRC_THREADS), 0, stream, wire_vars, 5 * (uint64_t)n,
                            (uint64_t)num_vars, d_flags + SOLVE_F_BAD_ID);
-        hipLaunchKernelGGL(solve_validate_kernel, dim3(var_tiles), dim3(CIRC_THREADS), 0, stream, def_gate, (uint64_t)num_vars, wire_vars, sel, (uint64_t)n, state,
-                           d_flags);
+        if (hints) {
+            hipLaunchKernelGGL(solve_hint_validate_kernel, dim3(var_tiles), dim3(CIRC_THREADS), 0, stream, def_gate, (uint64_t)num_vars, wire_vars, sel, hint_op,
+                               (uint64_t)n, state, d_flags);
+            hipLaunchKernelGGL(solve_hint_stray_kernel, dim3(circ_grid_of(n, CIRC_TILE)), dim3(CIRC_THREADS), 0, stream, hint_op, (uint64_t)n, (const uint32_t*)state,
+                               d_flags + SOLVE_F_STRAY);
+        } else {
+            hipLaunchKernelGGL(solve_validate_kernel, dim3(var_tiles), dim3(CIRC_THREADS), 0, stream, def_gate, (uint64_t)num_vars, wire_vars, sel, (uint64_t)n, state,
+                               d_flags);
+        }
         if ((rc = circ_launch_status("solve_validate"))) return rc;
-        HIP_TRY(hipMemcpyAsync(h, d_flags, sizeof(h), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(h, d_flags, flag_words * sizeof(*h), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         if (h[SOLVE_F_BAD_ID] != CIRC_NONE)
-            return plonk_fail(PLONK_ERR_ARG, "plonk_circuit_solve_dev: wire %llu of gate %llu reads a variable id >= num_vars = %zu", h[SOLVE_F_BAD_ID] / n,
+            return plonk_fail(PLONK_ERR_ARG, "%s: wire %llu of gate %llu reads a variable id >= num_vars = %zu", who, h[SOLVE_F_BAD_ID] / n,
                               h[SOLVE_F_BAD_ID] % n, num_vars);
         unsigned long long bad = CIRC_NONE;
         int why = 0;
         for (int f = SOLVE_F_BAD_GATE; f <= SOLVE_F_BAD_QECC; f++)
             if (h[f] < bad) { bad = h[f]; why = f; }
+        if (hints)
+            for (int f = SOLVE_F_BAD_OP; f <= SOLVE_F_BAD_ARG; f++)
+                if (h[f] < bad) { bad = h[f]; why = f; }
         if (why) {
             uint32_t g = 0;
             HIP_TRY(hipMemcpyAsync(&g, def_gate + bad, sizeof(g), hipMemcpyDeviceToHost, stream));
@@ -219,13 +252,21 @@ int circuit_solve_run(int curve, const uint32_t* wire_vars, size_t n, size_t num
             const char* what = why == SOLVE_F_BAD_GATE    ? "that gate is >= n"
                                : why == SOLVE_F_BAD_WIRE4 ? "wire 4 of that gate reads another variable"
                                : why == SOLVE_F_BAD_QO    ? "q_o is zero at that gate"
-                                                          : "q_ecc is not zero at that gate";
-            return plonk_fail(PLONK_ERR_ARG, "plonk_circuit_solve_dev: variable %llu is defined by gate %u, but %s (n = %zu)", bad, g, what, n);
+                               : why == SOLVE_F_BAD_QECC  ? "q_ecc is not zero at that gate"
+                               : why == SOLVE_F_BAD_OP    ? "hint_op there has an unknown opcode (1 INV, 2 DIV, 3 ROOT5, 4 BIT)"
+                                                          : "the BIT hint there has an argument >= 256";
+            return plonk_fail(PLONK_ERR_ARG, "%s: variable %llu is defined by gate %u, but %s (n = %zu)", who, bad, g, what, n);
         }
+        if (hints && h[SOLVE_F_STRAY] != CIRC_NONE)
+            return plonk_fail(PLONK_ERR_ARG, "%s: hint_op is not zero at gate %llu, which defines no variable", who, h[SOLVE_F_STRAY]);
         if (h[SOLVE_F_DEFINED] == 0) return PLONK_OK;
         HIP_TRY(hipMemsetAsync(start, 0xFF, num_vars * 4, stream));
-        hipLaunchKernelGGL(solve_keys_kernel, dim3(circ_grid_of(n, CIRC_THREADS)), dim3(CIRC_THREADS), 0, stream, wire_vars, def_gate, sel, (uint64_t)n, sentinel, state,
-                           keys[1], frontier[0], d_flags + SOLVE_F_COUNT0);
+        if (hints)
+            hipLaunchKernelGGL(solve_hint_keys_kernel, dim3(circ_grid_of(n, CIRC_THREADS)), dim3(CIRC_THREADS), 0, stream, wire_vars, def_gate, sel, hint_op, (uint64_t)n,
+                               sentinel, state, keys[1], frontier[0], d_flags + SOLVE_F_HCOUNT);
+        else
+            hipLaunchKernelGGL(solve_keys_kernel, dim3(circ_grid_of(n, CIRC_THREADS)), dim3(CIRC_THREADS), 0, stream, wire_vars, def_gate, sel, (uint64_t)n, sentinel, state,
+                               keys[1], frontier[0], d_flags + SOLVE_F_COUNT0);
         if ((rc = circ_launch_status("solve_keys"))) return rc;
     }
     const uint32_t* sk = keys[1];
@@ -238,12 +279,44 @@ int circuit_solve_run(int curve, const uint32_t* wire_vars, size_t n, size_t num
     }
     const uint64_t defined = h[SOLVE_F_DEFINED];
     uint64_t done = 0, depth = 0;
-    {
+    if (hints) {
+        // Per level: class 0 (gates, BIT), class 1 (INV, DIV) and class 2 (ROOT5) each in a launch of its own over its own list; all three read
+        // values of earlier levels only and release into the three lists of the other parity, whose sizes come back in one 24-byte read.
+        ProfScope ps("solve_levels", stream);
+        unsigned long long len[SOLVE_CLASSES] = {0, 0, 0};
+        auto read_counts = [&](const unsigned long long* d) -> int {
+            HIP_TRY(hipMemcpyAsync(len, d, sizeof(len), hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            return PLONK_OK;
+        };
+        if ((rc = read_counts(d_flags + SOLVE_F_HCOUNT))) return rc;
+        for (int cur = 0; len[0] + len[1] + len[2]; cur ^= 1) {
+            const unsigned long long all = len[0] + len[1] + len[2];
+            if (len[0] > n || len[1] > n || len[2] > n || all > defined - done)
+                return plonk_fail(PLONK_ERR_HIP, "%s: a frontier of %llu gates with %llu left", who, all, (unsigned long long)(defined - done));
+            unsigned long long* d_next = d_flags + SOLVE_F_HCOUNT + SOLVE_CLASSES * (cur ^ 1);
+            HIP_TRY(hipMemsetAsync(d_next, 0, sizeof(len), stream));
+            const uint32_t* fr = frontier[cur];
+            if (len[0])
+                hipLaunchKernelGGL(solve_hint_level_kernel, dim3(circ_grid_of(len[0], CIRC_THREADS)), dim3(CIRC_THREADS), 0, stream, fr, (uint64_t)len[0], wire_vars, sel, pub,
+                                   hint_op, (uint64_t)n, witness, sk, sv, N, (const uint32_t*)start, state, frontier[cur ^ 1], d_next, P);
+            if (len[1])
+                hipLaunchKernelGGL(solve_pow_kernel, dim3(circ_grid_of(len[1], CIRC_THREADS)), dim3(CIRC_THREADS), 0, stream, fr + n, (uint64_t)len[1], wire_vars, hint_op,
+                                   (uint64_t)n, witness, sk, sv, N, (const uint32_t*)start, state, frontier[cur ^ 1], d_next, e_inv, P);
+            if (len[2])
+                hipLaunchKernelGGL(solve_pow_kernel, dim3(circ_grid_of(len[2], CIRC_THREADS)), dim3(CIRC_THREADS), 0, stream, fr + 2 * n, (uint64_t)len[2], wire_vars, hint_op,
+                                   (uint64_t)n, witness, sk, sv, N, (const uint32_t*)start, state, frontier[cur ^ 1], d_next, e_root5, P);
+            if ((rc = circ_launch_status("solve_level"))) return rc;
+            done += all;
+            depth++;
+            if ((rc = read_counts(d_next))) return rc;
+        }
+    } else {
         ProfScope ps("solve_levels", stream);
         unsigned long long len = 0;
         if ((rc = circ_read_flag(d_flags + SOLVE_F_COUNT0, &len, stream))) return rc;
         for (int cur = 0; len; cur ^= 1) {
-            if (len > defined - done) return plonk_fail(PLONK_ERR_HIP, "plonk_circuit_solve_dev: a frontier of %llu gates with %llu left", len, (unsigned long long)(defined - done));
+            if (len > defined - done) return plonk_fail(PLONK_ERR_HIP, "%s: a frontier of %llu gates with %llu left", who, len, (unsigned long long)(defined - done));
             unsigned long long* d_next = d_flags + SOLVE_F_COUNT0 + (cur ^ 1);
             HIP_TRY(hipMemsetAsync(d_next, 0, sizeof(*d_next), stream));
             hipLaunchKernelGGL(solve_level_kernel, dim3(circ_grid_of(len, CIRC_THREADS)), dim3(CIRC_THREADS), 0, stream, (const uint32_t*)frontier[cur], (uint64_t)len,

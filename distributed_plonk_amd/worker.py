@@ -419,6 +419,15 @@ class PlonkWorker:
                                                C.byref(levels), C.byref(evals)))
         return unsolved.value, levels.value, evals.value
 
+    def circuit_solve_hints_dev(self, d_wire_vars: int, n: int, num_vars: int, d_selector_evals: int, d_pub_input: int, d_def_gate: int, d_hint_op: int,
+                                d_witness: int):
+        """circuit_solve_dev with hinted definitions (plonk_circuit_solve_hints_dev): d_hint_op u32 per gate, opcode in bits 0-7 (1 INV, 2 DIV,
+        3 ROOT5, 4 BIT), argument in bits 8-31, or 0 / None for none -> (unsolved_var or -1, levels, evaluations)."""
+        unsolved, levels, evals = C.c_int64(0), C.c_uint64(0), C.c_uint64(0)
+        check(self.lib.plonk_circuit_solve_hints_dev(self.ctx, d_wire_vars, n, num_vars, d_selector_evals, d_pub_input, d_def_gate, d_hint_op or None, d_witness,
+                                                     C.byref(unsolved), C.byref(levels), C.byref(evals)))
+        return unsolved.value, levels.value, evals.value
+
     def field_op(self, field: int, op: int, a: np.ndarray, b: Optional[np.ndarray] = None) -> np.ndarray:
         a = _u64(a)
         b = _u64(b) if b is not None else None

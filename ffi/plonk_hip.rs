@@ -159,6 +159,9 @@ extern "C" {
     pub fn plonk_circuit_solve_dev(ctx: *mut plonk_ctx, d_wire_vars: *const c_void, n: usize, num_vars: usize, d_selector_evals: *const c_void,
                                    d_pub_input: *const c_void, d_def_gate: *const c_void, d_witness: *mut c_void, unsolved_var: *mut i64,
                                    levels: *mut u64, evaluations: *mut u64) -> c_int;
+    pub fn plonk_circuit_solve_hints_dev(ctx: *mut plonk_ctx, d_wire_vars: *const c_void, n: usize, num_vars: usize, d_selector_evals: *const c_void,
+                                         d_pub_input: *const c_void, d_def_gate: *const c_void, d_hint_op: *const c_void, d_witness: *mut c_void,
+                                         unsolved_var: *mut i64, levels: *mut u64, evaluations: *mut u64) -> c_int;
     pub fn plonk_g2_generator(curve: c_int, out: *mut u64) -> c_int;
     pub fn plonk_g2_mul(curve: c_int, scalar: *const u64, input: *const u64, out: *mut u64) -> c_int;
     pub fn plonk_g2_check(curve: c_int, pt: *const u64, ok: *mut c_int) -> c_int;

@@ -359,6 +359,22 @@ int plonk_circuit_check_dev(plonk_ctx* ctx, const void* d_wires, const void* d_s
  * back by plonk_trim.  Synchronises. */
 int plonk_circuit_solve_dev(plonk_ctx* ctx, const void* d_wire_vars, size_t n, size_t num_vars, const void* d_selector_evals, const void* d_pub_input,
                             const void* d_def_gate, void* d_witness, int64_t* unsolved_var, uint64_t* levels, uint64_t* evaluations);
+/* plonk_circuit_solve_dev with HINTED definitions: values that no gate equation yields (an inverse, a fifth root, a bit), which a gate then only
+ * checks — division, is_zero, range checks, the inverse S-box of a Rescue round.  hint_op: u32 [n] or NULL; NULL is plonk_circuit_solve_dev
+ * itself (the same kernels, outputs and error texts).  hint_op[g]: bits 0-7 an opcode, bits 8-31 an argument; 0 = an ordinary gate.  A
+ * non-zero opcode makes g a hint gate: the variable on its wire 4 (def_gate[v] = g as above) is computed from the values s0 on wire 2 and s1
+ * on wire 3, and no selector of g is read — the selectors carry the check (typically q_o = 0 and a product or a power on wires 0-1):
+ *   1 INV    s0^-1, 0 for s0 = 0            2 DIV    s0 * s1^-1, 0 for s1 = 0
+ *   3 ROOT5  s0^d, d = 5^-1 mod (r - 1)     4 BIT    bit `arg` (< 256) of the canonical residue of s0; 0 at and above the field's bit length
+ * A hint gate depends on its source wires only (wire 2; wire 3 too for DIV): wires 0 and 1 are dead for scheduling whatever the selectors
+ * say and may read the gate's own output.  Levels and counters as above.  Checked on the device as above, except that q_o != 0 and
+ * q_ecc == 0 are not required at a hint gate; PLONK_ERR_ARG naming the variable and gate for an unknown opcode or a BIT argument >= 256, and
+ * naming the gate for a non-zero hint_op at a gate that defines no variable.  Per level the ordinary gates and BIT hints, the INV / DIV hints
+ * and the ROOT5 hints run as separate launches over separate lists (a power costs ~330 field products, a gate ~20).  Scratch: 4n u32 more than
+ * plonk_circuit_solve_dev.  Synchronises. */
+int plonk_circuit_solve_hints_dev(plonk_ctx* ctx, const void* d_wire_vars, size_t n, size_t num_vars, const void* d_selector_evals,
+                                  const void* d_pub_input, const void* d_def_gate, const void* d_hint_op, void* d_witness, int64_t* unsolved_var,
+                                  uint64_t* levels, uint64_t* evaluations);
 /* G2 and the pairing, host-only (no context, no GPU), for the verifier's last step e(A, [tau]_2) * e(-B, [1]_2) == 1 (jf-plonk's verify).
  * G2 points lie on the sextic twist (BN254: y^2 = x^3 + 3/(9+u), BLS12-381: y^2 = x^3 + 4(1+u); Fq2 = Fq[u]/(u^2+1)) and are encoded as
  * x.c0 || x.c1 || y.c0 || y.c1 Montgomery limbs (4Q u64), all zero = infinity; G1 points as x || y (2Q u64), (0, 0) = infinity.  Coordinates
