@@ -217,3 +217,19 @@ def test_host_side_point_functions_match_the_oracle(curve):
     assert affine(add(jac(bases[5]), jac(neg)))[1] is True                       # P - P
     assert same(add(zero, jac(bases[7])), jac(bases[7])) and same(add(jac(bases[7]), zero), jac(bases[7]))
     assert same(add(acc_l, acc_l), O.jac_add(curve, acc_o, acc_o))               # doubling of a non-normalised point
+
+
+def test_forced_plan_list_covers_every_pass_shape():
+    """tests/ntt_plans.py, the planner as the forced-plan GPU tests restate it, on their list of (ntt_max_log_r, log size): widths 2 ... 7 in
+    every position of a three-pass plan, the four-pass plans, and the plans the list was chosen for"""
+    from ntt_plans import FORCED_PLANS, plan_widths
+    plans = {(mx, L): plan_widths(L, mx) for mx, L in FORCED_PLANS}
+    assert plans[(3, 4)] == [2, 2] and plans[(3, 12)] == [3, 3, 3, 3] and plans[(4, 16)] == [4, 4, 4, 4] and plans[(5, 20)] == [5, 5, 5, 5]
+    assert plans[(6, 13)] == [5, 4, 4] and plans[(6, 16)] == [6, 5, 5] and plans[(6, 18)] == [6, 6, 6]
+    assert plans[(7, 15)] == [5, 5, 5] and plans[(7, 19)] == [7, 6, 6] and plans[(7, 21)] == [7, 7, 7]
+    three = [p for p in plans.values() if len(p) == 3]
+    for pos in range(3):                                      # the first pass is the widest and no plan is forced below 3: 2 leads only 2+2
+        assert {p[pos] for p in three} >= set(range(3 if pos == 0 else 2, 8)), (pos, sorted({p[pos] for p in three}))
+    four = [p for p in plans.values() if len(p) == 4]
+    assert {w for p in four for w in p[1:3]} >= {2, 3, 4, 5} and all(len(p) <= 4 for p in plans.values())
+    assert plan_widths(24, 9) == [8, 8, 8] and plan_widths(20, 9) == [7, 7, 6] and plan_widths(13, 3) == [3, 3, 3, 2, 2]

@@ -4,6 +4,8 @@ whole-domain coset FFT: the class s of G is exactly the stride-G slice of the re
 import numpy as np
 import pytest
 
+from ntt_plans import plan_widths
+
 pytestmark = pytest.mark.gpu
 
 
@@ -13,6 +15,31 @@ def _consts(oracle, cid, log_m):
     g = f.generator
     w_m = P.fr_from_limbs(f, oracle.field_const(cid, 0, 4, log_m))
     return P, f, g, w_m
+
+
+def _folded(P, f, g, poly, size):
+    """the coefficient vector whose size-point coset FFT (shift g) equals the evaluations of `poly`: zero-padded, or folded back when longer"""
+    length = len(poly)
+    folded = np.zeros((size, 4), dtype=np.uint64)
+    if length <= size:
+        folded[:length] = poly
+    else:                                                     # X^size = g^size on the coset: fold on the host with exact integers
+        c = pow(g, size, f.p)
+        acc = [0] * size
+        ints = [P.fr_from_limbs(f, x) for x in poly]
+        for i, v in enumerate(ints):
+            acc[i % size] = (acc[i % size] + v * pow(c, i // size, f.p)) % f.p
+        folded = np.stack([P.fr_to_limbs(f, v) for v in acc])
+    return folded
+
+
+def _class_plan(log_size, length, max_log_r):
+    """restates coset_eval_run's choice (csrc/poly_ops.hip): 2^k classes while another halving saves more than its folding costs, then the
+    pass widths of one class transform -> "<classes> x <w0+w1+...>" for assertion messages"""
+    k = 0
+    while k < 4 and log_size - k > 1 and 2 * length < 3 * ((1 << log_size) >> (k + 1)):
+        k += 1
+    return f"{1 << k} x " + "+".join(str(w) for w in plan_widths(log_size - k, max_log_r))
 
 
 @pytest.mark.parametrize("curve,cid", [("bn254", 0), ("bls12_381", 1)])
@@ -123,17 +150,7 @@ def test_coset_eval_zero_padding_classes_match_oracle(gpu_workers, oracle, curve
     size = 1 << log_size
     P, f, g, w_s = _consts(oracle, cid, log_size)
     poly = oracle.rand_fr(cid, 4000 + log_size, max(length, 1))[:length]
-    folded = np.zeros((size, 4), dtype=np.uint64)
-    if length <= size:
-        folded[:length] = poly
-    else:                                                     # X^size = g^size on the coset: fold on the host with exact integers
-        c = pow(g, size, f.p)
-        acc = [0] * size
-        ints = [P.fr_from_limbs(f, x) for x in poly]
-        for i, v in enumerate(ints):
-            acc[i % size] = (acc[i % size] + v * pow(c, i // size, f.p)) % f.p
-        folded = np.stack([P.fr_to_limbs(f, v) for v in acc])
-    want = oracle.ntt(cid, folded, False, True, threads=32)
+    want = oracle.ntt(cid, _folded(P, f, g, poly, size), False, True, threads=32)
     dp = w.alloc(max(length, 1) * 32)
     if length:
         dp.upload(poly)
@@ -144,6 +161,41 @@ def test_coset_eval_zero_padding_classes_match_oracle(gpu_workers, oracle, curve
     if length:
         assert np.array_equal(dp.download((length, 4)), poly)          # the input is not modified
     dp.free(); out.free()
+
+
+@pytest.mark.parametrize("curve,cid", [("bn254", 0), ("bls12_381", 1)])
+@pytest.mark.parametrize("max_log_r", [3, 4, 5])
+def test_coset_eval_and_interp_under_forced_plans(gpu_workers, oracle, curve, cid, max_log_r):
+    """The class transforms with the pass width capped by option ntt_max_log_r: first passes of width 3 and 4 (the shift sets of
+    plonk_coset_eval_dev are keyed by the first pass width, and no default plan has one below 5), 1 to 16 classes, with and without
+    folding, up to four passes per class; and plonk_coset_interp_dev over its whole range at 2^7 ... 2^12 points.  Bit-exact against
+    the oracle's coset FFT / coset iFFT of the zero-padded or folded vector."""
+    w = gpu_workers(curve)
+    try:
+        w.set_option("ntt_max_log_r", max_log_r)
+        for log_size, length in [(7, 19), (9, 67), (10, 131), (12, 515), (12, 4096), (12, 4099), (13, 5)]:
+            size = 1 << log_size
+            P, f, g, _ = _consts(oracle, cid, log_size)
+            poly = oracle.rand_fr(cid, 4100 + log_size, length)
+            want = oracle.ntt(cid, _folded(P, f, g, poly, size), False, True, threads=8)
+            dp, out = w.alloc(length * 32).upload(poly), w.alloc(size * 32)
+            w.coset_eval_dev(dp.ptr, length, size, P.fr_to_limbs(f, g), out.ptr)
+            where = f"{curve} coset_eval 2^{log_size} <- {length}: classes x plan {_class_plan(log_size, length, max_log_r)}"
+            assert np.array_equal(out.download((size, 4)), want), where
+            assert np.array_equal(dp.download((length, 4)), poly), where + " (input modified)"
+            dp.free(); out.free()
+        for log_m in range(7, 13):
+            m = 1 << log_m
+            P, f, g, _ = _consts(oracle, cid, log_m)
+            evals = oracle.rand_fr(cid, 4200 + log_m, m)
+            want = oracle.ntt(cid, evals, True, True, threads=8)        # coset_ifft: shift g, scale 1, every coefficient
+            de, out = w.alloc(m * 32).upload(evals), w.alloc(m * 32)
+            w.coset_interp_dev(de.ptr, m, P.fr_to_limbs(f, g), P.fr_to_limbs(f, 1), 0, m, out.ptr)
+            assert np.array_equal(out.download((m, 4)), want), f"{curve} coset_interp 2^{log_m}: plan {'+'.join(map(str, plan_widths(log_m, max_log_r)))}"
+            de.free(); out.free()
+    finally:
+        w.set_option("ntt_max_log_r", 9)
+        w.set_option("ntt_shoup", 1)
 
 
 def test_coset_eval_full_size_8n_against_independent_kernels(gpu_workers, oracle):

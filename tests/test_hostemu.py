@@ -9,7 +9,8 @@ orchestration and the N > 1 rank programs) is exercised and checked where no GPU
 wave-lockstep or memory-model effects are not — those remain with `pytest -m gpu` on an MI355X.  The emulation is test infrastructure:
 the package never loads it (`_ffi.lib()` refuses the library unless PLONK_ALLOW_HOSTEMU=1, which only this harness sets).
 
-The whole `-m gpu` suite under the emulation (≈ 25 min on 8 cores; everything but the full-size and torch.cuda-transport tests passes):
+The whole `-m gpu` suite under the emulation (≈ 25 min on 8 cores; everything but the full-size and torch.cuda-transport tests and
+test_gpu_limb_arith.py, which loads gfx950 code and has test_limb_harness_emu.py as its CPU twin, passes):
     python -m tests.hostemu.build && PLONK_HIP_LIB=tests/hostemu/_build/plain/libplonk_hostemu.so PLONK_ALLOW_HOSTEMU=1 \\
         HIPEMU_DEVICES=4 python -m pytest tests -m gpu -q
 """
@@ -59,6 +60,8 @@ def test_smoke_entry_point(emu_env):
 
 
 def test_field_ntt_golden_quotient_kernels(emu_env):
+    """test_gpu_ntt.py includes the plans forced with option ntt_max_log_r (every pass shape the planner can produce, four-pass plans, the
+    refusal of a fifth pass), up to 2^21 points"""
     _pytest(emu_env, ["tests/test_gpu_field.py", "tests/test_gpu_ntt.py", "tests/test_gpu_golden.py", "tests/test_gpu_quotient.py"])
 
 
@@ -97,8 +100,8 @@ def test_rank_programs_as_processes_world_2_and_4(emu_env):
 
 def test_distributed_transform_steps_and_coset_classes(emu_env):
     """fft_init / fft1 / fft2_prepare / fft2 per step against the oracle's helpers, S = 1, 2, 4 workloads in one process, the zero-padded row
-    pass up to 2^19, call-order errors; the zero-padding-aware coset FFT for every class count (the 2^20 + 3 case and the full-size
-    cross-check stay with the GPU)."""
+    pass up to 2^19, call-order errors; the zero-padding-aware coset FFT for every class count, also under forced plans with first passes
+    of width 3 and 4 (the 2^20 + 3 case and the full-size cross-check stay with the GPU)."""
     _pytest(emu_env, ["tests/test_gpu_distributed.py"], k="not (25-2 or 24-4 or 22-2 or rccl or two_contexts)")
     _pytest(emu_env, ["tests/test_gpu_coset_classes.py"], k="not full_size and not 1048579")
 
