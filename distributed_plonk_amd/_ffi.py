@@ -108,6 +108,8 @@ SIGNATURES = {
                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "plonk_circuit_solve_hints_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "plonk_rescue_permute_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    "plonk_rescue_merkle_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint]),
     "plonk_g2_generator": (C.c_int, [C.c_int, C.c_void_p]),
     "plonk_g2_mul": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "plonk_g2_check": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(C.c_int)]),

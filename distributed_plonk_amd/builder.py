@@ -20,6 +20,9 @@ Values that no gate equation yields — an inverse, a quotient, a fifth root, a 
 emit one gate whose selectors check the value and whose `hint_op` entry tells the device solver how to compute it from the gate's source
 wires (plonk_circuit_solve_hints_dev); `to_bits`, `range_check`, `is_zero`, `is_equal`, `select` and `less_than` are composed from them.
 
+Hashing: `rescue_permutation`, `rescue_hash2` and `merkle_root` emit the Rescue permutation of rescue.py (148 gates per instance, from `lc`,
+`root5` and `pow5_lc`), so a path of a rescue.MerkleTree built on the device is proved against its root.
+
 Field constants are Python ints (or sequences of them, one per gate), reduced mod r.  Gate equation and selector order: circuit.py.
 """
 from __future__ import annotations
@@ -423,6 +426,60 @@ class CircuitBuilder:
         d = self.lc([a, b], [1, -1], const=1 << nbits)
         top = self.to_bits(d, nbits + 1)[nbits]
         return self.lc([top], [-1], const=1)
+
+    # ------------------------------------------------------------------ Rescue (rescue.py: the same function on the device)
+    def _rescue_params(self, params):
+        from .rescue import RescueParams
+        if params is None:
+            return RescueParams.default(self.curve)
+        if not isinstance(params, RescueParams) or params.curve != self.curve:
+            raise ValueError(f"params: a rescue.RescueParams over {self.curve}")
+        return params
+
+    def _same_length(self, ids) -> list:
+        """ids checked and, if any of them is an array, all broadcast to that length (so that each emits one gate per instance)"""
+        vs = [self._var(v) for v in ids]
+        lens = sorted({v.shape[0] for v in vs if v.ndim})
+        k = max(lens, default=1)
+        if any(l not in (1, k) for l in lens):
+            raise ValueError(f"mismatched lengths {lens}: array arguments must have one length (or length 1)")
+        return [np.broadcast_to(v, (k,)) for v in vs] if lens else vs
+
+    def rescue_permutation(self, state4, params=None):
+        """The Rescue permutation of the state (s0, s1, s2, s3) -> its four output variables.  Per instance 4 lc gates for s + K[0], then per
+        round 4 root5 (the inverse S-boxes, hinted), 4 lc gates M y + K[2i+1] and 4 pow5_lc gates M (.)^5 + K[2i+2]: 148 gates, 37 levels."""
+        state4 = list(state4)
+        if len(state4) != 4:
+            raise ValueError(f"a state of {len(state4)} elements: Rescue's width is 4")
+        prm = self._rescue_params(params)
+        M, K = prm.mds, prm.round_keys
+        s = self._same_length(state4)
+        s = [self.lc([s[i]], [1], const=K[0][i]) for i in range(4)]
+        for rnd in range(len(K) // 2):
+            y = [self.root5(x) for x in s]
+            s = [self.lc(y, M[i], const=K[2 * rnd + 1][i]) for i in range(4)]
+            s = [self.pow5_lc(s, M[i], const=K[2 * rnd + 2][i]) for i in range(4)]
+        return s
+
+    def rescue_hash2(self, l, r, params=None):
+        """hash2(l, r) = rescue_permutation((l, r, 0, 0))[0]"""
+        return self.rescue_permutation([l, r, self.zero, self.zero], params)[0]
+
+    def merkle_root(self, leaf, index_bits, siblings, params=None):
+        """The root of the Merkle path from `leaf` up: siblings[j] is the other child at depth j (from the leaf), index_bits[j] = 1 where the
+        node on the path is the RIGHT child — rescue.MerkleTree.path's order.  Per depth: enforce_bool(bit), left = select(bit, sib, cur),
+        right = select(bit, cur, sib), cur = rescue_hash2(left, right).  -> the root variable(s); the caller equates it with the public root."""
+        index_bits, siblings = list(index_bits), list(siblings)
+        if len(index_bits) != len(siblings):
+            raise ValueError(f"mismatched lengths: {len(index_bits)} index bits, {len(siblings)} siblings")
+        prm = self._rescue_params(params)
+        self._same_length([leaf] + index_bits + siblings)
+        cur = leaf
+        for bit, sib in zip(index_bits, siblings):
+            self.enforce_bool(bit)
+            left, right = self.select(bit, sib, cur), self.select(bit, cur, sib)
+            cur = self.rescue_hash2(left, right, prm)
+        return cur
 
     # ------------------------------------------------------------------ constraints
     def enforce_equal(self, a, b):

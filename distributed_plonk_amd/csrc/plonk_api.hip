@@ -91,6 +91,8 @@ struct plonk_ctx {
     int comm_ordinal = 0;                       // this communicator's place among the device's communicators, in creation order (comm_order_check)
     int check_bases = 1;                        // init: every base must be a curve point (option "check_bases")
     unsigned long long* d_bad = nullptr;        // two words for that check's verdict
+    Fr* d_rescue = nullptr;                     // Rescue parameters (116 Fr) as last uploaded, and the host bytes they were uploaded from
+    std::vector<uint64_t> h_rescue;
 };
 
 // state of the collective order check (comm_order_check, further down)
@@ -215,6 +217,7 @@ extern "C" void plonk_destroy(plonk_ctx* ctx) {
     if (ctx->d_bases) (void)hipFree(ctx->d_bases);
     if (ctx->d_wire) (void)hipFree(ctx->d_wire);
     if (ctx->d_bad) (void)hipFree(ctx->d_bad);
+    if (ctx->d_rescue) (void)hipFree(ctx->d_rescue);
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
     if (ctx->d_scratch2) (void)hipFree(ctx->d_scratch2);
     msm_ws_release(ctx->msm_ws);
@@ -1273,6 +1276,35 @@ extern "C" int plonk_circuit_solve_hints_dev(plonk_ctx* ctx, const void* d_wire_
                                              uint64_t* levels, uint64_t* evaluations) {
     return circuit_solve_entry(ctx, d_wire_vars, n, num_vars, d_selector_evals, d_pub_input, d_def_gate, d_hint_op, d_witness, unsolved_var, levels, evaluations,
                                "plonk_circuit_solve_hints_dev");
+}
+// The Rescue parameters in the context's device buffer: uploaded when the bytes differ from the last upload.  The copy is ordered on the
+// stream behind the kernels that read the previous parameters, and reads the context's own host copy.
+static int rescue_params(plonk_ctx* ctx, const uint64_t* params) {
+    constexpr size_t WORDS = 116 * 4;
+    if (ctx->d_rescue && ctx->h_rescue.size() == WORDS && !memcmp(ctx->h_rescue.data(), params, WORDS * 8)) return PLONK_OK;
+    if (!ctx->d_rescue) HIP_TRY(hipMalloc((void**)&ctx->d_rescue, WORDS * 8));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));          // an earlier upload may still read h_rescue
+    ctx->h_rescue.assign(params, params + WORDS);
+    hipError_t e = hipMemcpyAsync(ctx->d_rescue, ctx->h_rescue.data(), WORDS * 8, hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) { ctx->h_rescue.clear(); HIP_TRY(e); }
+    return PLONK_OK;
+}
+extern "C" int plonk_rescue_permute_dev(plonk_ctx* ctx, const uint64_t* params, void* d_states, size_t count) {
+    CHECK_CTX(ctx);
+    if (!params || !d_states) return plonk_fail(PLONK_ERR_ARG, "plonk_rescue_permute_dev: null");
+    if (count == 0) return PLONK_OK;
+    int rc = rescue_params(ctx, params);
+    if (rc) return rc;
+    return rescue_permute_run(ctx->curve, ctx->d_rescue, (Fr*)d_states, count, ctx->stream, "plonk_rescue_permute_dev");
+}
+extern "C" int plonk_rescue_merkle_dev(plonk_ctx* ctx, const uint64_t* params, void* d_nodes, unsigned log_leaves) {
+    CHECK_CTX(ctx);
+    if (!params || !d_nodes) return plonk_fail(PLONK_ERR_ARG, "plonk_rescue_merkle_dev: null");
+    if (log_leaves > 31) return plonk_fail(PLONK_ERR_ARG, "plonk_rescue_merkle_dev: log_leaves = %u (at most 31)", log_leaves);
+    if (log_leaves == 0) return PLONK_OK;
+    int rc = rescue_params(ctx, params);
+    if (rc) return rc;
+    return rescue_merkle_run(ctx->curve, ctx->d_rescue, (Fr*)d_nodes, log_leaves, ctx->stream, "plonk_rescue_merkle_dev");
 }
 extern "C" int plonk_debug_field_op(plonk_ctx* ctx, int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
     CHECK_CTX(ctx);

@@ -238,6 +238,10 @@ size_t circuit_solve_scratch_bytes(size_t n, size_t num_vars, bool hints);
 int circuit_solve_run(int curve, const uint32_t* wire_vars, size_t n, size_t num_vars, const Fr* sel, const Fr* pub, const uint32_t* def_gate,
                       const uint32_t* hint_op, Fr* witness, int64_t* unsolved_var, uint64_t* levels, uint64_t* evaluations, void* scratch, hipStream_t stream,
                       const char* who);
+// Rescue (rescue_kernels.hpp, built in synth.hip).  params: 116 Fr on the device, the MDS matrix row-major then the 25 round keys; states:
+// [count][4] Fr in place, count > 0; nodes: 2^(log_leaves+1) - 1 Fr in heap order with the leaves filled, 1 <= log_leaves <= 31.  Enqueued only.
+int rescue_permute_run(int curve, const Fr* d_params, Fr* d_states, size_t count, hipStream_t stream, const char* who);
+int rescue_merkle_run(int curve, const Fr* d_params, Fr* d_nodes, unsigned log_leaves, hipStream_t stream, const char* who);
 
 // ----------------------------------------------------------------------------------------------- O(n) prover steps (poly_ops.hip, quotient.hip)
 int quotient_evals_run(NttTables& T, const plonk_quotient_inputs* in, size_t n, size_t m, const uint64_t* alpha, const uint64_t* beta,

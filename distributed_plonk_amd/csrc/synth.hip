@@ -360,6 +360,8 @@ int synth_circuit_dev(int curve, uint64_t seed, size_t n, size_t num_inputs, con
 #include "circuit_kernels.hpp"
 // the witness of such a circuit solved level by level from the gates that define its variables
 #include "solve_kernels.hpp"
+// the Rescue permutation and Merkle trees over it, on the solver's fixed-exponent power
+#include "rescue_kernels.hpp"
 
 // ---------------------------------------------------------------------------------------------- batched proof verification
 // the per-proof work of jf-plonk's verify / batch_verify up to the pairing: kernels and launcher in their own header

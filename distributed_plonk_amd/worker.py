@@ -428,6 +428,19 @@ class PlonkWorker:
                                                      C.byref(unsolved), C.byref(levels), C.byref(evals)))
         return unsolved.value, levels.value, evals.value
 
+    # ------------------------------------------------------------------ Rescue (distributed_plonk_amd/rescue.py)
+    def rescue_permute_dev(self, params: Optional[np.ndarray], d_states: int, count: int):
+        """The Rescue permutation of `count` states [count][4] Fr in place (plonk_rescue_permute_dev); params: (116, 4) Montgomery limbs, the MDS
+        matrix row-major then the 25 round keys.  Enqueued on the context's stream, not synchronised."""
+        p = None if params is None else _u64(params)
+        check(self.lib.plonk_rescue_permute_dev(self.ctx, _ptr(p), d_states or None, count))
+
+    def rescue_merkle_dev(self, params: Optional[np.ndarray], d_nodes: int, log_leaves: int):
+        """The inner nodes of a Merkle tree in heap order over the 2^log_leaves leaves at the end of d_nodes (plonk_rescue_merkle_dev).
+        Enqueued on the context's stream, not synchronised."""
+        p = None if params is None else _u64(params)
+        check(self.lib.plonk_rescue_merkle_dev(self.ctx, _ptr(p), d_nodes or None, log_leaves))
+
     def field_op(self, field: int, op: int, a: np.ndarray, b: Optional[np.ndarray] = None) -> np.ndarray:
         a = _u64(a)
         b = _u64(b) if b is not None else None

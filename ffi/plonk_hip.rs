@@ -10,7 +10,7 @@
 #![allow(non_camel_case_types, dead_code)]
 
 use std::ffi::CStr;
-use std::os::raw::{c_char, c_int, c_void};
+use std::os::raw::{c_char, c_int, c_uint, c_void};
 
 #[repr(C)]
 pub struct plonk_ctx {
@@ -162,6 +162,8 @@ extern "C" {
     pub fn plonk_circuit_solve_hints_dev(ctx: *mut plonk_ctx, d_wire_vars: *const c_void, n: usize, num_vars: usize, d_selector_evals: *const c_void,
                                          d_pub_input: *const c_void, d_def_gate: *const c_void, d_hint_op: *const c_void, d_witness: *mut c_void,
                                          unsolved_var: *mut i64, levels: *mut u64, evaluations: *mut u64) -> c_int;
+    pub fn plonk_rescue_permute_dev(ctx: *mut plonk_ctx, params: *const u64, d_states: *mut c_void, count: usize) -> c_int;
+    pub fn plonk_rescue_merkle_dev(ctx: *mut plonk_ctx, params: *const u64, d_nodes: *mut c_void, log_leaves: c_uint) -> c_int;
     pub fn plonk_g2_generator(curve: c_int, out: *mut u64) -> c_int;
     pub fn plonk_g2_mul(curve: c_int, scalar: *const u64, input: *const u64, out: *mut u64) -> c_int;
     pub fn plonk_g2_check(curve: c_int, pt: *const u64, ok: *mut c_int) -> c_int;

@@ -375,6 +375,20 @@ int plonk_circuit_solve_dev(plonk_ctx* ctx, const void* d_wire_vars, size_t n, s
 int plonk_circuit_solve_hints_dev(plonk_ctx* ctx, const void* d_wire_vars, size_t n, size_t num_vars, const void* d_selector_evals,
                                   const void* d_pub_input, const void* d_def_gate, const void* d_hint_op, void* d_witness, int64_t* unsolved_var,
                                   uint64_t* levels, uint64_t* evaluations);
+/* The Rescue permutation on the device, the one builder.py's rescue_permutation proves: state s in Fr^4, alpha = 5, 12 rounds (jellyfish's
+ * structure),
+ *   s <- s + K[0];   12 times:  s <- M (s_j^(1/5))_j + K[2i+1],   s <- M (s_j^5)_j + K[2i+2]        x^(1/5) = x^d, d = 5^-1 mod (r - 1); 0 -> 0
+ * and hash2(l, r) = permute((l, r, 0, 0))[0].  params: HOST, 116 Fr Montgomery = M row-major (16) then K[0..24] (100; K[t][i] at 16 + 4t + i),
+ * kept in a context-owned device buffer and uploaded again only when the bytes differ from the last call's (distributed_plonk_amd/rescue.py
+ * derives the project's default parameters).  d_states: [count][4] Fr Montgomery, permuted in place, one lane per state (~16.6 k field products
+ * each).  Ordered on the context's stream; returns once the work is enqueued (plonk_sync, or any synchronising call, waits for it).  count = 0
+ * is a no-op.  PLONK_ERR_ARG for a NULL params or d_states. */
+int plonk_rescue_permute_dev(plonk_ctx* ctx, const uint64_t* params, void* d_states, size_t count);
+/* A Merkle tree over 2^log_leaves leaves with hash2 above, in heap order in one buffer of 2^(log_leaves+1) - 1 Fr: node 0 is the root, the
+ * children of node m are 2m+1 (left) and 2m+2 (right), leaf i is node 2^log_leaves - 1 + i.  The leaves are filled on entry; every inner node
+ * is written, node[m] = hash2(node[2m+1], node[2m+2]): log_leaves launches, bottom-up, on the context's stream; returns once they are
+ * enqueued.  log_leaves = 0 is a no-op (the leaf is the root).  PLONK_ERR_ARG for a NULL params or d_nodes, or log_leaves > 31. */
+int plonk_rescue_merkle_dev(plonk_ctx* ctx, const uint64_t* params, void* d_nodes, unsigned log_leaves);
 /* G2 and the pairing, host-only (no context, no GPU), for the verifier's last step e(A, [tau]_2) * e(-B, [1]_2) == 1 (jf-plonk's verify).
  * G2 points lie on the sextic twist (BN254: y^2 = x^3 + 3/(9+u), BLS12-381: y^2 = x^3 + 4(1+u); Fq2 = Fq[u]/(u^2+1)) and are encoded as
  * x.c0 || x.c1 || y.c0 || y.c1 Montgomery limbs (4Q u64), all zero = infinity; G1 points as x || y (2Q u64), (0, 0) = infinity.  Coordinates
