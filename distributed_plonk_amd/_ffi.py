@@ -110,6 +110,9 @@ SIGNATURES = {
                                                 C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "plonk_rescue_permute_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "plonk_rescue_merkle_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint]),
+    "plonk_rescue_acc_build_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p]),
+    "plonk_rescue_acc_paths_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "plonk_circuit_scatter_inputs_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t]),
     "plonk_g2_generator": (C.c_int, [C.c_int, C.c_void_p]),
     "plonk_g2_mul": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "plonk_g2_check": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(C.c_int)]),

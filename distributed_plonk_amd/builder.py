@@ -21,7 +21,9 @@ emit one gate whose selectors check the value and whose `hint_op` entry tells th
 wires (plonk_circuit_solve_hints_dev); `to_bits`, `range_check`, `is_zero`, `is_equal`, `select` and `less_than` are composed from them.
 
 Hashing: `rescue_permutation`, `rescue_hash2` and `merkle_root` emit the Rescue permutation of rescue.py (148 gates per instance, from `lc`,
-`root5` and `pow5_lc`), so a path of a rescue.MerkleTree built on the device is proved against its root.
+`root5` and `pow5_lc`), so a path of a rescue.MerkleTree built on the device is proved against its root; `rescue_hash3` and `accumulator_root`
+do the same for the ternary rescue.Accumulator (membership.py builds the reference's generate_circuit shape from them).  Inputs that are
+already on the device — a rescue.Accumulator's witness_inputs_dev — go into a solve as `d_inputs=` and never visit the host.
 
 Field constants are Python ints (or sequences of them, one per gate), reduced mod r.  Gate equation and selector order: circuit.py.
 """
@@ -61,6 +63,7 @@ class BuiltCircuit:
         if self.hint_op.shape != (wire_vars.shape[1],):
             raise ValueError(f"hint_op of shape {self.hint_op.shape} for {wire_vars.shape[1]} gates")
         self._dev = None                              # (worker, [wire_vars, selector_evals, def_gate(, hint_op)] device buffers)
+        self._dev_input_vars = None                   # input_vars as u32 on the same worker, once a solve took d_inputs
 
     @property
     def n(self) -> int:
@@ -96,16 +99,23 @@ class BuiltCircuit:
             for b in self._dev[1]:
                 b.free()
             self._dev = None
+        if self._dev_input_vars is not None:
+            self._dev_input_vars.free()
+            self._dev_input_vars = None
 
-    def solve_dev(self, worker: PlonkWorker, inputs, public_inputs=None) -> "SolvedWitness":
+    def solve_dev(self, worker: PlonkWorker, inputs=None, public_inputs=None, *, d_inputs: Optional[int] = None) -> "SolvedWitness":
         """inputs: (len(input_vars), 4), public_inputs: (num_public, 4) Montgomery limbs.  The circuit is uploaded once per worker and kept
-        (close() frees it); the witness buffer gets the inputs and zero, the device fills in every defined variable.  Raises
-        circuit.UnsolvableCircuit naming the smallest variable on a dependency cycle.  -> SolvedWitness (device buffers; close() it)."""
+        (close() frees it); the witness buffer gets the inputs and zero, the device fills in every defined variable.  d_inputs, instead of
+        `inputs`: a device pointer to the same (len(input_vars), 4) values, scattered into the witness buffer on the device
+        (plonk_circuit_scatter_inputs_dev).  Raises circuit.UnsolvableCircuit naming the smallest variable on a dependency cycle.
+        -> SolvedWitness (device buffers; close() it)."""
         if worker.curve_name != self.curve:
             raise ValueError(f"circuit over {self.curve}, worker over {worker.curve_name}")
+        if d_inputs is not None and inputs is not None:
+            raise ValueError("inputs and d_inputs: one of them")
         inp = np.ascontiguousarray(np.zeros((0, 4)) if inputs is None else inputs, dtype=np.uint64).reshape(-1, 4)
         pub = np.ascontiguousarray(np.zeros((0, 4)) if public_inputs is None else public_inputs, dtype=np.uint64).reshape(-1, 4)
-        if inp.shape[0] != len(self.input_vars):
+        if d_inputs is None and inp.shape[0] != len(self.input_vars):
             raise ValueError(f"{inp.shape[0]} input values for {len(self.input_vars)} inputs")
         if pub.shape[0] != self.num_public:
             raise ValueError(f"{pub.shape[0]} public input values for {self.num_public} public inputs")
@@ -113,10 +123,17 @@ class BuiltCircuit:
         n = self.n
         out = SolvedWitness(worker, self, d_vars.ptr, d_sel.ptr)
         try:
-            witness = np.zeros((self.num_vars, 4), dtype=np.uint64)
-            witness[self.input_vars] = inp
-            out.d_witness.upload(witness)
-            del witness
+            if d_inputs is None:
+                witness = np.zeros((self.num_vars, 4), dtype=np.uint64)
+                witness[self.input_vars] = inp
+                out.d_witness.upload(witness)
+                del witness
+            else:
+                if self._dev_input_vars is None:
+                    ids = np.ascontiguousarray(self.input_vars, dtype=np.uint32)
+                    self._dev_input_vars = worker.alloc(max(4, ids.nbytes)).upload(ids)
+                worker.memset_dev(out.d_witness.ptr, 0, self.num_vars * 32)
+                worker.circuit_scatter_inputs_dev(self._dev_input_vars.ptr, len(self.input_vars), d_inputs, out.d_witness.ptr, self.num_vars)
             worker.memset_dev(out.d_pub.ptr, 0, n * 32)
             if self.num_public:
                 out.d_pub.upload(pub)
@@ -133,10 +150,11 @@ class BuiltCircuit:
             raise
         return out
 
-    def preprocess(self, worker: PlonkWorker, inputs, public_inputs=None, check: bool = True, k: Optional[np.ndarray] = None) -> _circuit.PreprocessedCircuit:
+    def preprocess(self, worker: PlonkWorker, inputs=None, public_inputs=None, check: bool = True, k: Optional[np.ndarray] = None, *,
+                   d_inputs: Optional[int] = None) -> _circuit.PreprocessedCircuit:
         """solve_dev, then circuit.preprocess_dev on the same device buffers.  check: the satisfiability kernel validates every gate, the
         constraints included, so a wrong input raises circuit.UnsatisfiedCircuit."""
-        s = self.solve_dev(worker, inputs, public_inputs)
+        s = self.solve_dev(worker, inputs, public_inputs, d_inputs=d_inputs)
         try:
             return _circuit.preprocess_dev(worker, s.d_wire_vars, self.n, self.num_vars, s.d_witness.ptr, s.d_selector_evals, s.d_pub.ptr, self.num_public,
                                            k, check)
@@ -479,6 +497,34 @@ class CircuitBuilder:
             self.enforce_bool(bit)
             left, right = self.select(bit, sib, cur), self.select(bit, cur, sib)
             cur = self.rescue_hash2(left, right, prm)
+        return cur
+
+    def rescue_hash3(self, a, b, c, params=None):
+        """hash3(a, b, c) = rescue_permutation((a, b, c, 0))[0]"""
+        return self.rescue_permutation([a, b, c, self.zero], params)[0]
+
+    def accumulator_root(self, uid, elem, sib1s, sib2s, is_lefts, is_rights, params=None):
+        """The root of the path of leaf (uid, elem) through a ternary accumulator (rescue.Accumulator; jellyfish's compute_merkle_root):
+        cur = rescue_hash3(zero, uid, elem), then per level j, from the leaves up, with the two other members sib1s[j], sib2s[j] of the group
+        in ascending position and the flags is_lefts[j], is_rights[j] (cur is the left / the right member; neither: the middle one):
+            enforce_bool(is_left), enforce_bool(is_right), enforce_bool(is_left + is_right)
+            l = select(is_left, cur, sib1),  r = select(is_right, cur, sib2),  mid = cur + sib1 + sib2 - l - r,  cur = rescue_hash3(l, mid, r)
+        — 148 + 8 gates per level after the 148 of the leaf.  The flags are NOT tied to uid, exactly as in jellyfish: the circuit proves that
+        SOME position sequence leads from the leaf hash, which contains uid, to the root.  -> the root variable(s); the caller equates it
+        with the public root."""
+        lists = [list(x) for x in (sib1s, sib2s, is_lefts, is_rights)]
+        if len({len(x) for x in lists}) != 1:
+            raise ValueError(f"mismatched lengths: {', '.join(str(len(x)) for x in lists)} sib1s, sib2s, is_lefts, is_rights")
+        prm = self._rescue_params(params)
+        self._same_length([uid, elem] + [v for x in lists for v in x])
+        cur = self.rescue_hash3(self.zero, uid, elem, prm)
+        for sib1, sib2, is_left, is_right in zip(*lists):
+            self.enforce_bool(is_left)
+            self.enforce_bool(is_right)
+            self.enforce_bool(self.add(is_left, is_right))
+            l, r = self.select(is_left, cur, sib1), self.select(is_right, cur, sib2)
+            mid = self.sub(self.lc([cur, sib1, sib2, l], [1, 1, 1, -1]), r)
+            cur = self.rescue_hash3(l, mid, r, prm)
         return cur
 
     # ------------------------------------------------------------------ constraints

@@ -1306,6 +1306,52 @@ extern "C" int plonk_rescue_merkle_dev(plonk_ctx* ctx, const uint64_t* params, v
     if (rc) return rc;
     return rescue_merkle_run(ctx->curve, ctx->d_rescue, (Fr*)d_nodes, log_leaves, ctx->stream, "plonk_rescue_merkle_dev");
 }
+// height in 1 .. 40 and count in 1 .. 3^height (3^40 < 2^64)
+static int rescue_acc_shape(size_t count, unsigned height, const char* who) {
+    if (height == 0 || height > 40) return plonk_fail(PLONK_ERR_ARG, "%s: height = %u (1 .. 40)", who, height);
+    uint64_t cap = 1;
+    for (unsigned j = 0; j < height; j++) cap *= 3;
+    if (count == 0 || (uint64_t)count > cap) return plonk_fail(PLONK_ERR_ARG, "%s: count = %zu (1 .. 3^height = %llu)", who, count, (unsigned long long)cap);
+    return PLONK_OK;
+}
+extern "C" int plonk_rescue_acc_build_dev(plonk_ctx* ctx, const uint64_t* params, const void* d_elems, size_t count, unsigned height, void* d_nodes) {
+    CHECK_CTX(ctx);
+    if (!params) return plonk_fail(PLONK_ERR_ARG, "plonk_rescue_acc_build_dev: params is null");
+    if (!d_elems) return plonk_fail(PLONK_ERR_ARG, "plonk_rescue_acc_build_dev: d_elems is null");
+    if (!d_nodes) return plonk_fail(PLONK_ERR_ARG, "plonk_rescue_acc_build_dev: d_nodes is null");
+    int rc = rescue_acc_shape(count, height, "plonk_rescue_acc_build_dev");
+    if (rc) return rc;
+    if ((rc = rescue_params(ctx, params))) return rc;
+    return rescue_acc_build_run(ctx->curve, ctx->d_rescue, (const Fr*)d_elems, count, height, (Fr*)d_nodes, ctx->stream, "plonk_rescue_acc_build_dev");
+}
+extern "C" int plonk_rescue_acc_paths_dev(plonk_ctx* ctx, const void* d_nodes, size_t count, unsigned height, const void* d_elems, const void* d_uids, size_t m,
+                                          void* d_inputs_out) {
+    CHECK_CTX(ctx);
+    if (!d_nodes) return plonk_fail(PLONK_ERR_ARG, "plonk_rescue_acc_paths_dev: d_nodes is null");
+    if (!d_elems) return plonk_fail(PLONK_ERR_ARG, "plonk_rescue_acc_paths_dev: d_elems is null");
+    if (!d_uids) return plonk_fail(PLONK_ERR_ARG, "plonk_rescue_acc_paths_dev: d_uids is null");
+    if (!d_inputs_out) return plonk_fail(PLONK_ERR_ARG, "plonk_rescue_acc_paths_dev: d_inputs_out is null");
+    int rc = rescue_acc_shape(count, height, "plonk_rescue_acc_paths_dev");
+    if (rc) return rc;
+    if (m == 0) return PLONK_OK;
+    if ((uint64_t)m > 0xFFFFFFFFull) return plonk_fail(PLONK_ERR_ARG, "plonk_rescue_acc_paths_dev: m = %zu (at most 2^32 - 1)", m);
+    if ((rc = ensure_scratch2(ctx, 64))) return rc;
+    return rescue_acc_paths_run(ctx->curve, (const Fr*)d_nodes, count, height, (const Fr*)d_elems, (const uint64_t*)d_uids, m, (Fr*)d_inputs_out, ctx->d_scratch2,
+                                ctx->stream, "plonk_rescue_acc_paths_dev");
+}
+extern "C" int plonk_circuit_scatter_inputs_dev(plonk_ctx* ctx, const void* d_input_vars, size_t num_inputs, const void* d_inputs, void* d_witness, size_t num_vars) {
+    CHECK_CTX(ctx);
+    if (!d_input_vars) return plonk_fail(PLONK_ERR_ARG, "plonk_circuit_scatter_inputs_dev: d_input_vars is null");
+    if (!d_inputs) return plonk_fail(PLONK_ERR_ARG, "plonk_circuit_scatter_inputs_dev: d_inputs is null");
+    if (!d_witness) return plonk_fail(PLONK_ERR_ARG, "plonk_circuit_scatter_inputs_dev: d_witness is null");
+    if (num_vars == 0 || num_vars > 0xFFFFFFFEull)
+        return plonk_fail(PLONK_ERR_ARG, "plonk_circuit_scatter_inputs_dev: num_vars = %zu (ids are u32 with one sentinel: 1 .. 2^32 - 2)", num_vars);
+    if (num_inputs == 0) return PLONK_OK;
+    int rc = ensure_scratch2(ctx, 64);
+    if (rc) return rc;
+    return circuit_scatter_inputs_run((const uint32_t*)d_input_vars, num_inputs, (const Fr*)d_inputs, (Fr*)d_witness, num_vars, ctx->d_scratch2, ctx->stream,
+                                      "plonk_circuit_scatter_inputs_dev");
+}
 extern "C" int plonk_debug_field_op(plonk_ctx* ctx, int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
     CHECK_CTX(ctx);
     if (!a || !out) return plonk_fail(PLONK_ERR_ARG, "plonk_debug_field_op: null");

@@ -242,6 +242,14 @@ int circuit_solve_run(int curve, const uint32_t* wire_vars, size_t n, size_t num
 // [count][4] Fr in place, count > 0; nodes: 2^(log_leaves+1) - 1 Fr in heap order with the leaves filled, 1 <= log_leaves <= 31.  Enqueued only.
 int rescue_permute_run(int curve, const Fr* d_params, Fr* d_states, size_t count, hipStream_t stream, const char* who);
 int rescue_merkle_run(int curve, const Fr* d_params, Fr* d_nodes, unsigned log_leaves, hipStream_t stream, const char* who);
+// The ternary accumulator (rescue_acc_kernels.hpp, built in synth.hip): 1 <= height <= 40, 1 <= count <= 3^height; nodes: the levels one after
+// another from the leaves up.  build is enqueued only; paths (m >= 1) and the input scatter (num_inputs >= 1) read a verdict back and
+// synchronise; scratch: 8 bytes.
+int rescue_acc_build_run(int curve, const Fr* d_params, const Fr* d_elems, uint64_t count, unsigned height, Fr* d_nodes, hipStream_t stream, const char* who);
+int rescue_acc_paths_run(int curve, const Fr* d_nodes, uint64_t count, unsigned height, const Fr* d_elems, const uint64_t* d_uids, uint64_t m, Fr* d_out, void* scratch,
+                         hipStream_t stream, const char* who);
+int circuit_scatter_inputs_run(const uint32_t* d_input_vars, size_t num_inputs, const Fr* d_inputs, Fr* d_witness, size_t num_vars, void* scratch, hipStream_t stream,
+                               const char* who);
 
 // ----------------------------------------------------------------------------------------------- O(n) prover steps (poly_ops.hip, quotient.hip)
 int quotient_evals_run(NttTables& T, const plonk_quotient_inputs* in, size_t n, size_t m, const uint64_t* alpha, const uint64_t* beta,

@@ -362,6 +362,8 @@ int synth_circuit_dev(int curve, uint64_t seed, size_t n, size_t num_inputs, con
 #include "solve_kernels.hpp"
 // the Rescue permutation and Merkle trees over it, on the solver's fixed-exponent power
 #include "rescue_kernels.hpp"
+// the ternary accumulator over it, its membership paths, and the scatter that starts a solve from inputs on the device
+#include "rescue_acc_kernels.hpp"
 
 // ---------------------------------------------------------------------------------------------- batched proof verification
 // the per-proof work of jf-plonk's verify / batch_verify up to the pairing: kernels and launcher in their own header

@@ -441,6 +441,21 @@ class PlonkWorker:
         p = None if params is None else _u64(params)
         check(self.lib.plonk_rescue_merkle_dev(self.ctx, _ptr(p), d_nodes or None, log_leaves))
 
+    def rescue_acc_build_dev(self, params: Optional[np.ndarray], d_elems: int, count: int, height: int, d_nodes: int):
+        """The ternary accumulator of the `count` elems at d_elems (plonk_rescue_acc_build_dev): d_nodes receives the levels one after another
+        from the leaves up, the root last.  Enqueued on the context's stream, not synchronised."""
+        p = None if params is None else _u64(params)
+        check(self.lib.plonk_rescue_acc_build_dev(self.ctx, _ptr(p), d_elems or None, count, height, d_nodes or None))
+
+    def rescue_acc_paths_dev(self, d_nodes: int, count: int, height: int, d_elems: int, d_uids: int, m: int, d_inputs_out: int):
+        """The membership witnesses of the m uids (u64) at d_uids, (2 + 4 height) rows of m Fr at d_inputs_out: uid, elem, then per level sib1,
+        sib2, is_left, is_right (plonk_rescue_acc_paths_dev).  Synchronises."""
+        check(self.lib.plonk_rescue_acc_paths_dev(self.ctx, d_nodes or None, count, height, d_elems or None, d_uids or None, m, d_inputs_out or None))
+
+    def circuit_scatter_inputs_dev(self, d_input_vars: int, num_inputs: int, d_inputs: int, d_witness: int, num_vars: int):
+        """witness[input_vars[k]] = inputs[k] on the device (plonk_circuit_scatter_inputs_dev); d_input_vars: u32.  Synchronises."""
+        check(self.lib.plonk_circuit_scatter_inputs_dev(self.ctx, d_input_vars or None, num_inputs, d_inputs or None, d_witness or None, num_vars))
+
     def field_op(self, field: int, op: int, a: np.ndarray, b: Optional[np.ndarray] = None) -> np.ndarray:
         a = _u64(a)
         b = _u64(b) if b is not None else None

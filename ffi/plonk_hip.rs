@@ -164,6 +164,9 @@ extern "C" {
                                          unsolved_var: *mut i64, levels: *mut u64, evaluations: *mut u64) -> c_int;
     pub fn plonk_rescue_permute_dev(ctx: *mut plonk_ctx, params: *const u64, d_states: *mut c_void, count: usize) -> c_int;
     pub fn plonk_rescue_merkle_dev(ctx: *mut plonk_ctx, params: *const u64, d_nodes: *mut c_void, log_leaves: c_uint) -> c_int;
+    pub fn plonk_rescue_acc_build_dev(ctx: *mut plonk_ctx, params: *const u64, d_elems: *const c_void, count: usize, height: c_uint, d_nodes: *mut c_void) -> c_int;
+    pub fn plonk_rescue_acc_paths_dev(ctx: *mut plonk_ctx, d_nodes: *const c_void, count: usize, height: c_uint, d_elems: *const c_void, d_uids: *const c_void, m: usize, d_inputs_out: *mut c_void) -> c_int;
+    pub fn plonk_circuit_scatter_inputs_dev(ctx: *mut plonk_ctx, d_input_vars: *const c_void, num_inputs: usize, d_inputs: *const c_void, d_witness: *mut c_void, num_vars: usize) -> c_int;
     pub fn plonk_g2_generator(curve: c_int, out: *mut u64) -> c_int;
     pub fn plonk_g2_mul(curve: c_int, scalar: *const u64, input: *const u64, out: *mut u64) -> c_int;
     pub fn plonk_g2_check(curve: c_int, pt: *const u64, ok: *mut c_int) -> c_int;

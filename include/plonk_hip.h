@@ -389,6 +389,30 @@ int plonk_rescue_permute_dev(plonk_ctx* ctx, const uint64_t* params, void* d_sta
  * is written, node[m] = hash2(node[2m+1], node[2m+2]): log_leaves launches, bottom-up, on the context's stream; returns once they are
  * enqueued.  log_leaves = 0 is a no-op (the leaf is the root).  PLONK_ERR_ARG for a NULL params or d_nodes, or log_leaves > 31. */
 int plonk_rescue_merkle_dev(plonk_ctx* ctx, const uint64_t* params, void* d_nodes, unsigned log_leaves);
+/* The ternary Rescue accumulator: jellyfish's sparse, append-only 3-ary Merkle tree, the one the reference's test circuit proves memberships
+ * in (generate_circuit, dispatcher2.rs:1226-1271: TREE_HEIGHT = 32, 50 leaves at uids 0 .. 49).  With hash3(a, b, c) = permute((a, b, c, 0))[0]:
+ *   level 0    c_0 = count nodes:               node_0[i]     = hash3(0, i, elems[i])             (the uid i as a field element)
+ *   level j+1  c_{j+1} = ceil(c_j / 3) nodes:   node_{j+1}[t] = hash3(x_0, x_1, x_2),  x_k = node_j[3t+k] if 3t+k < c_j, else 0
+ * for j < height.  An empty subtree is 0 (not hash3(0, 0, 0)) and no all-empty node is computed.  d_nodes: sum_{j <= height} c_j Fr (at most
+ * 1.5 count + height), the levels one after another from the leaves up: offset_0 = 0, offset_{j+1} = offset_j + c_j; the root is the last
+ * element.  d_elems: count Fr, Montgomery; params as for plonk_rescue_permute_dev.  One launch for the leaves, one per level with more than
+ * one node, and ONE for the chain hash3(x, 0, 0) above the first level of one node.  Ordered on the context's stream; returns once the work
+ * is enqueued.  PLONK_ERR_ARG naming the argument for a NULL pointer, height outside 1 .. 40, count outside 1 .. 3^height. */
+int plonk_rescue_acc_build_dev(plonk_ctx* ctx, const uint64_t* params, const void* d_elems, size_t count, unsigned height, void* d_nodes);
+/* The membership witnesses of m uids of a built accumulator, written where a solve takes them from.  d_uids: u64 [m].  For level j < height
+ * the node on the path of uid i is number q = floor(i / 3^j) of the level, pos_j = q mod 3 its position in the group of three from
+ * g = 3 floor(i / 3^(j+1)) on; sib1_j, sib2_j are the two OTHER members of the group in ascending position (0 beyond c_j),
+ * is_left_j = [pos_j = 0], is_right_j = [pos_j = 2] as field 0 / 1.  d_inputs_out: (2 + 4 height) rows of m Fr, row-major: the uids as field
+ * elements, elems[uid], then per level sib1_j, sib2_j, is_left_j, is_right_j — the order in which distributed_plonk_amd/membership.py creates
+ * the inputs of its circuit.  m = 0 is a no-op.  PLONK_ERR_ARG as above, and naming the first k with d_uids[k] >= count (checked on the device;
+ * nothing is written for such a k).  Synchronises. */
+int plonk_rescue_acc_paths_dev(plonk_ctx* ctx, const void* d_nodes, size_t count, unsigned height, const void* d_elems, const void* d_uids, size_t m,
+                               void* d_inputs_out);
+/* witness[input_vars[k]] = inputs[k], k < num_inputs: the given variables of plonk_circuit_solve_dev's witness from values already on the
+ * device.  d_input_vars: u32 [num_inputs]; d_inputs: num_inputs Fr; d_witness: num_vars Fr.  num_inputs = 0 is a no-op.  PLONK_ERR_ARG for a
+ * NULL pointer, num_vars outside 1 .. 2^32 - 2, and naming the first k with input_vars[k] >= num_vars (checked on the device; nothing is
+ * written for such a k).  Synchronises. */
+int plonk_circuit_scatter_inputs_dev(plonk_ctx* ctx, const void* d_input_vars, size_t num_inputs, const void* d_inputs, void* d_witness, size_t num_vars);
 /* G2 and the pairing, host-only (no context, no GPU), for the verifier's last step e(A, [tau]_2) * e(-B, [1]_2) == 1 (jf-plonk's verify).
  * G2 points lie on the sextic twist (BN254: y^2 = x^3 + 3/(9+u), BLS12-381: y^2 = x^3 + 4(1+u); Fq2 = Fq[u]/(u^2+1)) and are encoded as
  * x.c0 || x.c1 || y.c0 || y.c1 Montgomery limbs (4Q u64), all zero = infinity; G1 points as x || y (2Q u64), (0, 0) = infinity.  Coordinates

@@ -1,9 +1,12 @@
-"""Rate of the Rescue kernels (csrc/rescue_kernels.hpp) on one GPU.
+"""Rate of the Rescue kernels (csrc/rescue_kernels.hpp, csrc/rescue_acc_kernels.hpp) on one GPU.
 
     python tools/rescue_probe.py [--log 20] [--curve bn254 bls12_381] [--reps 7] [--out profiles/rescue_probe.txt]
 
 Times 2^log permutations (plonk_rescue_permute_dev, one launch) and a tree over 2^log leaves (plonk_rescue_merkle_dev, `log` launches,
 2^log - 1 hashes) from the HIP events the library records around its own launches (plonk_profile_*: "rescue_permute", "rescue_merkle").
+The accumulator leg times plonk_rescue_acc_build_dev ("rescue_acc_build") at 2^log elems and height 32 — one permutation per node, the
+launches counted as (levels with more than one node) + 2 — and the reference's own case, 50 elems at height 32: 104 permutations of which
+the last 28 are ONE lane's chain in one launch, so that build is bounded by one lane's permutation latency, reported as us per chain link.
 Inputs are generated on the device from a seed.  One warm-up run of each (it loads the code object and uploads the parameters), then
 `reps` timed runs: the median, the smallest and the largest, in milliseconds, and from the median the permutations per second and the
 implied field products per second at 12 x (4 x 335 + 12 + 32) = 16608 products per permutation (335: solve_hints.hpp's own count of
@@ -20,6 +23,7 @@ from distributed_plonk_amd import rescue as RS  # noqa: E402
 from distributed_plonk_amd.worker import PlonkWorker  # noqa: E402
 
 PRODUCTS = 12 * (4 * 335 + 12 + 32)
+ACC_HEIGHT = 32
 
 
 def timed(w: PlonkWorker, name: str, call, reps: int) -> list:
@@ -54,8 +58,17 @@ def probe(curve: str, log: int, reps: int) -> list:
         try:
             w.synth_fr(1, buf.ptr, 4 * count)
             lines.append(line(f"2^{log} permutations, one launch", count, timed(w, "rescue_permute", lambda: RS.permute_dev(w, prm, buf.ptr, count), reps)))
+            lines.append(line("1 permutation, one launch: one lane's latency", 1, timed(w, "rescue_permute", lambda: RS.permute_dev(w, prm, buf.ptr, 1), reps)))
             lines.append(line(f"tree over 2^{log} leaves, {log} launches, {count - 1} hashes", count - 1,
                               timed(w, "rescue_merkle", lambda: RS.merkle_dev(w, prm, buf.ptr, log), reps)))
+            for n_elems in (count, 50):
+                counts = RS.acc_level_counts(ACC_HEIGHT, n_elems)
+                nodes, wide = sum(counts), sum(c > 1 for c in counts)
+                ms = timed(w, "rescue_acc_build", lambda: RS.acc_build_dev(w, prm, buf.ptr, n_elems, ACC_HEIGHT, buf.offset(count * 32)), reps)
+                med = statistics.median(ms)
+                chain = counts.count(1) - 1
+                lines.append(line(f"accumulator of {n_elems} elems, height {ACC_HEIGHT}: {wide + 2} launches, {nodes} permutations, a chain of {chain}", nodes, ms)
+                             + f"; {med * 1e6 / nodes:.0f} ns per permutation" + (f", at most {med * 1e3 / chain:.0f} us per chain link" if n_elems == 50 else ""))
         finally:
             buf.free()
     finally:
@@ -73,7 +86,7 @@ def main():
     lines = [f"tools/rescue_probe.py --log {a.log} --reps {a.reps}: HIP events around the library's own launches, one MI355X"]
     for curve in a.curve:
         lines += probe(curve, a.log, a.reps)
-        print("\n".join(lines[-3:]), flush=True)
+        print("\n".join(lines[-6:]), flush=True)
     if a.out:
         with open(a.out, "w") as fh:
             fh.write("\n".join(lines) + "\n")
