@@ -14,36 +14,12 @@ from distributed_plonk_amd._ffi import PlonkError
 from distributed_plonk_amd.prover import Prover
 from distributed_plonk_amd.synthetic import SyntheticInstance
 from distributed_plonk_amd.transcript import PlonkTranscript
+from tests.circuit_cases import _blinders, _proved
 
 pytestmark = pytest.mark.gpu
 
 CURVES = [("bn254", 0), ("bls12_381", 1)]
 TAU = 0x0123456789ABCDEF_FEDCBA9876543210_0F1E2D3C4B5A6978_1122334455667788 >> 3
-_CACHE = {}
-
-
-def _blinders(oracle, cid, seed):
-    return dict(wires=oracle.rand_fr(cid, seed, 10).reshape(5, 2, 4), perm=oracle.rand_fr(cid, seed + 1, 3))
-
-
-def _proved(gpu_workers, oracle, curve, cid, log_n=10, nproofs=3, seed=3):
-    """(worker, vk, public inputs, [proofs with different blinders]) of one synthetic instance under the trapdoor key; cached."""
-    key = (curve, log_n, nproofs, seed)
-    if key not in _CACHE:
-        w = gpu_workers(curve)
-        inst = SyntheticInstance(w, log_n, seed=seed, num_inputs=3, tau=TAU)
-        pv = Prover(w, log_n)
-        try:
-            pv.load_key_dev(inst.sel_ptrs, inst.sig_ptrs, inst.k)
-            pub = inst.public_inputs()
-            proofs = [pv.prove_dev(inst.wev, inst.d_id.ptr, inst.d_idx.ptr, inst.d_pi.ptr, _blinders(oracle, cid, 40 + 3 * i), pv.fiat_shamir(pub))
-                      for i in range(nproofs)]
-            vk = copy.deepcopy(pv.verifying_key())
-        finally:
-            pv.close()
-            inst.close()
-        _CACHE[key] = (vk, pub, proofs)
-    return (gpu_workers(curve),) + _CACHE[key]
 
 
 def _ref_ok(curve, vk, pub, proof, tau=TAU):

@@ -12,42 +12,12 @@ from distributed_plonk_amd.prover import Prover
 from distributed_plonk_amd.synthetic import SyntheticInstance, wire_subset_separators
 from distributed_plonk_amd.transcript import PlonkTranscript
 from distributed_plonk_amd import fr as _fr
+from tests.circuit_cases import ref_id_perm, ref_perm_idx, wiring
 
 pytestmark = pytest.mark.gpu
 
 CURVES = [("bn254", 0), ("bls12_381", 1)]
 TAU = 0x0123456789ABCDEF_FEDCBA9876543210_0F1E2D3C4B5A6978_1122334455667788 >> 3
-
-
-def ref_perm_idx(wire_vars: np.ndarray) -> np.ndarray:
-    """jellyfish compute_wire_permutation: the positions of one variable in increasing order form a cycle, the last links to the first."""
-    flat = np.asarray(wire_vars, dtype=np.int64).reshape(-1)
-    order = np.argsort(flat, kind="stable")
-    sv = flat[order]
-    nxt = np.roll(order, -1)
-    starts = np.flatnonzero(np.r_[True, sv[1:] != sv[:-1]])
-    ends = np.r_[starts[1:], len(sv)] - 1
-    nxt[ends] = order[starts]
-    out = np.empty(flat.size, dtype=np.uint64)
-    out[order] = nxt.astype(np.uint64)
-    return out
-
-
-def ref_id_perm(oracle, cid: int, n: int, k: np.ndarray) -> np.ndarray:
-    """k_i * w^j by vector doubling of the powers of w (oracle field ops)."""
-    from oracle import bigint_ref as B
-    from oracle import prover_ref as P
-    f = P.CURVE_OBJ[cid].fr
-    g = B.Radix2Domain(f, n).group_gen
-    pw = np.zeros((n, 4), dtype=np.uint64)
-    pw[0] = P.fr_to_limbs(f, 1)
-    filled = 1
-    while filled < n:
-        cnt = min(filled, n - filled)
-        step = np.broadcast_to(P.fr_to_limbs(f, pow(g, filled, f.p)), (cnt, 4)).copy()
-        pw[filled:filled + cnt] = oracle.field_op(cid, 0, "mul", pw[:cnt], step)
-        filled += cnt
-    return np.concatenate([oracle.field_op(cid, 0, "mul", pw, np.broadcast_to(k[i], (n, 4)).copy()) for i in range(5)])
 
 
 def run_permutation(w, wire_vars: np.ndarray, num_vars: int, k: np.ndarray):
@@ -61,23 +31,6 @@ def run_permutation(w, wire_vars: np.ndarray, num_vars: int, k: np.ndarray):
     finally:
         for b in (dv, did, didx, dsig):
             b.free()
-
-
-def wiring(kind: str, n: int, seed: int):
-    rs = np.random.RandomState(seed)
-    if kind == "identity":
-        return np.arange(5 * n, dtype=np.uint32).reshape(5, n), 5 * n
-    if kind == "single":
-        return np.zeros((5, n), dtype=np.uint32), 1
-    if kind == "random":
-        nv = max(2, 2 * n)
-        return rs.randint(0, nv, size=(5, n)).astype(np.uint32), nv
-    if kind == "heavy":                      # half the positions on variable 0, like padding
-        nv = max(2, n)
-        wv = rs.randint(1, nv, size=5 * n).astype(np.uint32)
-        wv[rs.permutation(5 * n)[:5 * n // 2]] = 0
-        return wv.reshape(5, n), nv
-    raise ValueError(kind)
 
 
 @pytest.mark.parametrize("curve,cid", CURVES)

@@ -19,8 +19,9 @@ from distributed_plonk_amd import verifier as VF
 from distributed_plonk_amd._ffi import PlonkError
 from distributed_plonk_amd.prover import Prover
 from distributed_plonk_amd.transcript import PlonkTranscript
+from tests.circuit_cases import random_layered, random_layered_hints
 from tests.hint_ref import GIVEN, HintRefSolver
-from tests.test_gpu_solve import TAU, random_layered, trapdoor_key
+from tests.test_gpu_solve import TAU, trapdoor_key
 
 pytestmark = pytest.mark.gpu
 
@@ -73,58 +74,6 @@ def raw_solve(w, built, inputs=None, hint_op="own", entry="hints", wire_vars=Non
     finally:
         for x in bufs:
             x.free()
-
-
-def random_layered_hints(curve: str, log_n: int, seed: int):
-    """-> (BuiltCircuit of 2^log_n gates after padding, input residues, public-input residues).  Rounds of `width` gates, the old builder
-    operations and the hinted ones in turn, operands drawn from everything defined so far; 0, 1 and r - 1 are among the input values."""
-    rnd = random.Random(seed)
-    rs = np.random.RandomState(seed)
-    p = _fr.FIELDS[curve].p
-    n = 1 << log_n
-    small = ["inv", "div", "root5", "bit", "add"]
-    medium = ["add", "inv_or_zero", "mul", "inv", "pow5_lc", "div", "gate", "root5", "lc", "bit", "is_zero", "select", "to_bits", "sub", "mul_add", "is_equal"]
-    cost = {"is_zero": 3, "to_bits": 7, "is_equal": 4, "less_than": 19}   # gates per element
-    kinds = small if log_n == 3 else medium if log_n == 5 else medium + ["less_than"]
-    per_width = sum(cost.get(k, 1) for k in kinds)
-    width = 1 if log_n <= 5 else (n - 3) // per_width
-    b = BD.CircuitBuilder(curve)
-    pub = b.public_input()
-    ins = b.input(3 * width)
-    pool = np.concatenate([[b.zero, b.one, pub], ins])
-    pick = lambda: pool[rs.randint(0, len(pool), size=width)]
-    coef = lambda: [rnd.randrange(p) for _ in range(width)]
-    for kind in kinds:
-        before = b.num_gates
-        if kind in ("add", "sub", "mul", "div", "is_equal"):
-            new = getattr(b, kind)(pick(), pick())
-        elif kind in ("inv", "inv_or_zero", "root5", "is_zero"):
-            new = getattr(b, kind)(pick())
-        elif kind == "bit":
-            new = b.bit(pick(), rs.randint(0, 256, size=width))
-        elif kind == "select":
-            new = b.select(pick(), pick(), pick())                          # c need not be boolean for the solver
-        elif kind == "to_bits":
-            new = np.concatenate([np.atleast_1d(v) for v in b.to_bits(pick(), 5)])      # mostly unsatisfied: the solver does not look at constraints
-        elif kind == "less_than":
-            new = b.less_than(pick(), pick(), 4)
-        elif kind == "lc":
-            new = b.lc([pick(), pick(), pick(), pick()], [coef(), rnd.randrange(p), coef(), -1], const=coef())
-        elif kind == "mul_add":
-            new = b.mul_add(pick(), pick(), pick(), pick(), q0=coef(), q1=rnd.randrange(p))
-        elif kind == "pow5_lc":
-            new = b.pow5_lc([pick(), pick(), pick()], [coef(), 1, coef()], const=rnd.randrange(p))
-        else:
-            q_o = [(1, p - 1, rnd.randrange(1, p))[min(rnd.randrange(4), 2)] for _ in range(width)]
-            sel = {name: coef() for name in BD.SELECTOR_INDEX if name not in ("q_o",)}
-            new = b.gate([pick(), pick(), pick(), pick()], {**sel, "q_o": q_o})
-        assert b.num_gates - before == cost.get(kind, 1) * width, kind
-        pool = np.concatenate([pool, np.atleast_1d(new)])
-    built = b.build()
-    assert built.n == n, (built.n, n)
-    inputs = [rnd.randrange(p) for _ in range(len(built.input_vars))]
-    inputs[:3] = [0, 1, p - 1]
-    return built, inputs, [rnd.randrange(p)]
 
 
 # ---------------------------------------------------------------------------------------------- against the reference

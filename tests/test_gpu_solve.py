@@ -17,6 +17,7 @@ from distributed_plonk_amd import verifier as VF
 from distributed_plonk_amd._ffi import PlonkError
 from distributed_plonk_amd.prover import Prover
 from distributed_plonk_amd.transcript import PlonkTranscript
+from tests.circuit_cases import random_layered
 from tests.solve_ref import GIVEN, RefSolver
 
 pytestmark = pytest.mark.gpu
@@ -28,52 +29,6 @@ INDEPENDENT_LOG = 20
 
 
 # ---------------------------------------------------------------------------------------------- circuits
-def random_layered(curve: str, log_n: int, seed: int):
-    """-> (BuiltCircuit of exactly 2^log_n gates after padding, input residues, public-input residues).  Rounds of `width` gates, every
-    operation of the builder in turn, operands drawn from everything defined so far; gate() with 12 random selectors and q_o random,
-    1 or -1; constraint gates (not solved for, some unsatisfied) in between."""
-    rnd = random.Random(seed)
-    rs = np.random.RandomState(seed)
-    p = _fr.FIELDS[curve].p
-    n = 1 << log_n
-    rounds, width, tail = (5, 1, False) if log_n == 3 else (14, ((n - 7) // 14), True)
-    b = BD.CircuitBuilder(curve)
-    pub = b.public_input()
-    ins = b.input(3 * width)
-    pool = np.concatenate([[b.zero, b.one, pub], ins])
-    pick = lambda: pool[rs.randint(0, len(pool), size=width)]
-    coef = lambda: [rnd.randrange(p) for _ in range(width)]
-    kinds = ["add", "sub", "mul", "lc", "mul_add", "pow5_lc", "gate"]
-    for r in range(rounds):
-        kind = kinds[r % len(kinds)]
-        if kind == "add":
-            new = b.add(pick(), pick())
-        elif kind == "sub":
-            new = b.sub(pick(), pick())
-        elif kind == "mul":
-            new = b.mul(pick(), pick())
-        elif kind == "lc":
-            new = b.lc([pick(), pick(), pick(), pick()], [coef(), rnd.randrange(p), coef(), -1], const=coef())
-        elif kind == "mul_add":
-            new = b.mul_add(pick(), pick(), pick(), pick(), q0=coef(), q1=rnd.randrange(p))
-        elif kind == "pow5_lc":
-            new = b.pow5_lc([pick(), pick(), pick()], [coef(), 1, coef()], const=rnd.randrange(p))
-        else:
-            q_o = [(1, p - 1, rnd.randrange(1, p))[min(rnd.randrange(4), 2)] for _ in range(width)]
-            sel = {name: coef() for name in BD.SELECTOR_INDEX if name not in ("q_o",)}
-            new = b.gate([pick(), pick(), pick(), pick()], {**sel, "q_o": q_o})
-        pool = np.concatenate([pool, np.atleast_1d(new)])
-    if tail:
-        x, y = int(pool[-1]), int(pool[-2])
-        b.enforce_equal(x, x)
-        b.enforce_mul(x, y, int(pool[-3]))                  # not satisfied: the solver does not look at constraints
-        b.enforce_bool(b.one)
-        b.enforce_constant(b.one, 1)
-    built = b.build()
-    assert built.n == n, (built.n, n)
-    return built, [rnd.randrange(p) for _ in range(len(built.input_vars))], [rnd.randrange(p)]
-
-
 def solve_and_compare(w, built, inputs, publics):
     """the device witness against the reference, bit for bit, and the counters; -> the device witness"""
     ref = RefSolver(built, inputs, publics)

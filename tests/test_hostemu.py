@@ -327,10 +327,21 @@ def test_bench_plain_run_is_the_headline_alone(emu_env, tmp_path, headline):
 
 def test_differential_fuzz_slice(emu_env):
     """A fixed-seed slice of tools/fuzz_abi.py (random operations, shapes, flags and options against the oracle); long runs are a manual tool —
-    nineteen operations, from single kernels to whole proofs handed to the verifier; under AddressSanitizer it found the two defects recorded in DESIGN §5 and docs/HISTORY.md §0."""
-    r = subprocess.run([sys.executable, "tools/fuzz_abi.py", "--seconds", "500", "--max-ops", "60", "--seed", "5", "--max-log", "10"], cwd=ROOT, env=emu_env,
-                       capture_output=True, text=True, timeout=900)
+    `--ops core`: the nineteen operations of the MSM / NTT / prover side, from single kernels to whole proofs handed to the verifier; under
+    AddressSanitizer it found the two defects recorded in DESIGN §5 and docs/HISTORY.md §0."""
+    r = subprocess.run([sys.executable, "tools/fuzz_abi.py", "--seconds", "500", "--max-ops", "60", "--seed", "5", "--max-log", "10", "--ops", "core"], cwd=ROOT,
+                       env=emu_env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "fuzz ok: 60 operations" in r.stdout, (r.stdout + r.stderr)[-2000:]
+
+
+def test_differential_fuzz_slice_of_the_circuit_operations(emu_env):
+    """The fuzzer's `circuit` group — circuit preprocessing, the witness solver with and without hints, Rescue permutations and Merkle trees, the
+    ternary accumulator and its path gather, the batched verifier, the membership chain — with plonk_trim, transforms and polynomial operations
+    between them, on one long-lived (emulated) context, against tests/solve_ref.py, hint_ref.py, rescue_ref.py, accumulator_ref.py and
+    oracle/verifier_ref.py.  This is the part of tests/test_gpu_fuzz_slice.py that runs where no GPU exists."""
+    r = subprocess.run([sys.executable, "tools/fuzz_abi.py", "--seconds", "800", "--max-ops", "20", "--seed", "7", "--max-log", "8", "--ops", "circuit,trim,ntt,poly"],
+                       cwd=ROOT, env=emu_env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "fuzz ok: 20 operations" in r.stdout, (r.stdout + r.stderr)[-2000:]
 
 
 def test_second_device_of_one_process_raises_its_own_lds_limits(emu_env):

@@ -1,14 +1,27 @@
 #!/usr/bin/env python3
-"""Differential fuzzing of the C ABI against the CPU oracle: random operations with random shapes, flags and options — sizes that
+"""Differential fuzzing of the C ABI against CPU references: random operations with random shapes, flags and options — sizes that
 are not in any fixed test list (odd lengths, single elements, lengths around the class / pass / slice boundaries), special field
-values, repeated and infinite bases, forced Pippenger windows — every result compared bit-for-bit with the oracle.
+values, repeated and infinite bases, forced Pippenger windows — on ONE long-lived context per curve, with plonk_trim, re-inits and
+forced options in between, every result compared bit-for-bit with its reference.
 
-    python tools/fuzz_abi.py --seconds 600 [--seed 1] [--curve bn254|bls12_381|both] [--max-log 13]
+    python tools/fuzz_abi.py --seconds 600 [--seed 1] [--curve bn254|bls12_381|both] [--max-log 13] [--ops NAME[,NAME...]] [--only NAME] [--trace]
+
+Twenty-five operations in two groups.  `core` (nineteen, against oracle/oracle.py): transforms, MSMs and batched commitments, polynomial
+operations, the grand product, quotient evaluations, distributed transforms, refused SRSs, trim, whole proofs handed to the verifier.
+`circuit` (six): circuit_preprocess (plonk_circuit_permutation_dev / _witness_dev / _check_dev against a stable argsort and a big-integer gate
+evaluation), solve (the level-by-level witness solver, plain or hinted, against tests/solve_ref.py / hint_ref.py, with planted cycles,
+refused definitions and the witness carried into preprocessing), rescue (permutation and Merkle kernels against tests/rescue_ref.py,
+default and injected parameters by coin), accumulator (the ternary tree and its path gather against tests/accumulator_ref.py),
+verify_batch (plonk_verify_batch_dev on batches of honest and mutated proofs against oracle/verifier_ref.py) and membership (accumulator,
+gather, solve, preprocess, prove, verify, then a spoiled instance).  --ops takes operation and group names and draws from that list
+(default: all; `--ops core` is draw for draw the fuzzer as it was before the circuit group); --only runs one operation.  Whatever --max-log
+says, a circuit operation stays below 2^12 gates and about 200 reference Rescue permutations, so that no draw waits long for its reference.
 
 It drives whatever library `distributed_plonk_amd._ffi` loads: libplonk_hip.so on an MI355X, or — in the GPU-less build container —
 the host emulation (tests/hostemu; PLONK_HIP_LIB=tests/hostemu/_build/plain/libplonk_hostemu.so PLONK_ALLOW_HOSTEMU=1), where it
 is also worth running against the AddressSanitizer build.  The first mismatch prints the operation and its parameters (enough to
-replay it with --seed / --only) and exits 1.  tests/test_hostemu.py runs a short fixed-seed slice of it in the CPU suite.
+replay it with --seed and the same --ops / --only) and exits 1; a HIP error or any unexpected exception ends the run.
+tests/test_hostemu.py runs two short fixed-seed slices of it in the CPU suite, tests/test_gpu_fuzz_slice.py five on the device.
 """
 import argparse
 import os
@@ -34,6 +47,17 @@ class Fuzz:
         self.max_log = max_log
         self.counter = 0
         self.n_bases = 0
+        self.proved = None                            # op_verify_batch's proved instance
+        self.membership_built = {}                    # op_membership's circuits under the default parameters, by (height, m)
+        self.key_epoch = 0                            # counts the installs of a commit key on self.w, whichever operation made them
+        for name in ("init", "init_dev"):
+            setattr(self.w, name, self._counting(getattr(self.w, name)))
+
+    def _counting(self, install):
+        def counted(*args, **kwargs):
+            self.key_epoch += 1
+            return install(*args, **kwargs)
+        return counted
 
     # ---------------------------------------------------------------- inputs
     def seed(self):
@@ -611,14 +635,654 @@ class Fuzz:
             buf.free(); out.free()
         return np.array_equal(got, want[off::G] if G > 1 else want), dict(log_n=log_n, variant=variant, G=G, off=off)
 
-    OPS = ["ntt", "coset_eval_interp", "msm", "commit_many", "poly", "lincomb", "perm_product", "transpose", "distributed_fft", "quotient", "compact_rows_fft", "round1", "prove_verify", "class_prove", "msm_table",
-           "perm_product_ranges", "class_ifft", "init_refuses_bad_srs", "trim"]
+    # ---------------------------------------------------------------- circuits, witnesses, Rescue trees, the verifier
+    # The caps below (2^12 gates, about 200 reference permutations, 8 distinct verifier records) are properties of these operations, not of
+    # --max-log: they bound what one draw spends in its pure-Python reference.
+    def ints(self, limbs):
+        f = self.f
+        return [int.from_bytes(row.tobytes(), "little") * f.R_inv % f.p for row in np.ascontiguousarray(limbs, dtype=np.uint64).reshape(-1, 4)]
+
+    def limbs(self, values):
+        f = self.f
+        raw = b"".join((int(x) % f.p * f.R % f.p).to_bytes(32, "little") for x in values)
+        return np.frombuffer(raw, dtype=np.uint64).reshape(-1, 4).copy()
+
+    def rescue_params(self):
+        """(RescueParams, the reference's params or None, "default" | "injected"): by coin the project's default tables or freshly drawn ones, so
+        that successive operations flip the context's cached parameter block back and forth"""
+        from distributed_plonk_amd import rescue as RS
+        if self.rs.rand() < 0.5:
+            return RS.RescueParams.default(self.curve), None, "default"
+        vals = self.ints(self.O.rand_fr(self.cid, self.seed(), RS.NUM_PARAMS))
+        M = [vals[4 * i:4 * i + 4] for i in range(4)]
+        K = [vals[16 + 4 * t:20 + 4 * t] for t in range(RS.NUM_KEYS)]
+        return RS.RescueParams(self.curve, M, K), (M, K), "injected"
+
+    def op_circuit_preprocess(self):
+        """plonk_circuit_permutation_dev / _witness_dev / _check_dev on a random wiring: perm_idx, id_perm and the sigma columns against the
+        stable-argsort reference, witness placement against a numpy gather, the check on a satisfying witness and on one planted violation
+        (a gate's q_c, or one wire value), both first-bad indices against a big-integer evaluation of the gate equation."""
+        from distributed_plonk_amd.synthetic import wire_subset_separators
+        from tests.circuit_cases import ref_id_perm, ref_perm_idx, wiring
+        f, p, rs = self.f, self.f.p, self.rs
+        log_n = int(rs.randint(1, min(self.max_log, 12) + 1))
+        n = 1 << log_n
+        case = int(rs.randint(0, 5))
+        if case == 0:
+            nv = 1
+        elif case == 1:
+            nv = int(rs.randint(1, n + 1))
+        elif case == 2:                                               # the radix pass counts
+            nv = int(rs.choice([255, 256, 257, 65535, 65536, 65537]))
+        elif case == 3:
+            nv = 5 * n + int(rs.randint(1, 4 * n + 2))               # some ids unused
+        else:
+            nv = int(rs.randint(1, 6 * n + 1))
+        kind = str(rs.choice(["identity", "single", "random", "heavy", "same", "once", "uniform"]))
+        wseed = self.seed()
+        if kind == "same":                                            # every wire the same variable
+            wv = np.full((5, n), int(rs.randint(0, nv)), dtype=np.uint32)
+        elif kind == "once":                                          # each variable exactly once
+            nv = max(nv, 5 * n)
+            wv = rs.permutation(nv)[:5 * n].astype(np.uint32).reshape(5, n)
+        elif kind == "uniform":
+            wv = rs.randint(0, nv, size=(5, n)).astype(np.uint32)
+            wv[int(rs.randint(0, 5)), int(rs.randint(0, n))] = nv - 1
+        else:
+            wv, used = wiring(kind, n, wseed)
+            nv = max(nv, used)
+        info = dict(log_n=log_n, num_vars=nv, kind=kind, wseed=wseed)
+        k = wire_subset_separators(f, wseed)
+        wit = self.fr(nv)
+        m = int(rs.randint(0, min(n, 3) + 1))
+        pub = np.zeros((n, 4), dtype=np.uint64)
+        pub[:m] = self.fr(m)
+        # selectors: twelve random columns (sparse now and then), q_c solved so that every gate holds
+        sel = self.fr(13 * n).reshape(13, n, 4)
+        if rs.rand() < 0.3:
+            sel[:, ::2] = 0
+        wires = wit[wv.astype(np.int64)]                              # the numpy gather
+        wi = [self.ints(wires[i]) for i in range(5)]
+        si = [self.ints(sel[t]) for t in range(13)]
+        pi = self.ints(pub)
+
+        def residual(g, q_c=None):
+            w = [wi[i][g] for i in range(5)]
+            acc = (si[11][g] if q_c is None else q_c) + pi[g] + si[4][g] * w[0] * w[1] + si[5][g] * w[2] * w[3]
+            for i in range(4):
+                acc += si[i][g] * w[i] + si[6 + i][g] * pow(w[i], 5, p)
+            return (acc + si[12][g] * w[0] * w[1] * w[2] * w[3] * w[4] - si[10][g] * w[4]) % p
+
+        for g in range(n):
+            si[11][g] = (-residual(g, 0)) % p
+        sel[11] = self.limbs(si[11])
+        want_idx = ref_perm_idx(wv)
+        want_id = ref_id_perm(self.O, self.cid, n, k)
+        bufs = [self.up(wv), self.w.alloc(5 * n * 32), self.w.alloc(5 * n * 8), self.w.alloc(5 * n * 32), self.up(wit), self.w.alloc(5 * n * 32),
+                self.up(sel), self.up(pub)]
+        dv, did, didx, dsig, dwit, dw, dsel, dpub = bufs
+        try:
+            self.w.circuit_permutation_dev(dv.ptr, n, nv, k, did.ptr, didx.ptr, dsig.ptr)
+            self.w.circuit_witness_dev(dv.ptr, n, dwit.ptr, nv, dw.ptr)
+            got = self.w.circuit_check_dev(dw.ptr, dsel.ptr, dpub.ptr, didx.ptr, n)
+            info["what"] = "permutation"
+            ok = (np.array_equal(didx.download((5 * n,)), want_idx) and np.array_equal(did.download((5 * n, 4)), want_id)
+                  and np.array_equal(dsig.download((5 * n, 4)), want_id[want_idx.astype(np.int64)]))
+            if ok:
+                info["what"] = "witness placement"
+                ok = np.array_equal(dw.download((5, n, 4)), wires)
+            if ok:
+                info["what"] = "check of a satisfied witness"
+                ok = got == (-1, -1)
+            if ok and rs.rand() < 0.5:                                # a gate violation, gates 0 and n - 1 included
+                g = int(rs.choice([0, n - 1, int(rs.randint(0, n))]))
+                si[11][g] = (si[11][g] + 1 + int(rs.randint(0, 1 << 30))) % p
+                self.w.write_bytes(dsel.ptr + (11 * n + g) * 32, f.to_limbs(si[11][g]))
+                info.update(what="planted gate violation", gate=g)
+                ok = self.w.circuit_check_dev(dw.ptr, dsel.ptr, dpub.ptr, didx.ptr, n) == (g, -1) and residual(g) != 0
+            elif ok:                                                  # one wire value changed: its gate and its copy cycle
+                pos = int(rs.randint(0, 5 * n))
+                i, g = pos // n, pos % n
+                new = (wi[i][g] + 1 + int(rs.randint(0, 1 << 30))) % p
+                wi[i][g] = new
+                flat = wires.reshape(5 * n, 4).copy()
+                flat[pos] = f.to_limbs(new)
+                self.w.write_bytes(dw.ptr + pos * 32, flat[pos])
+                bad_gates = [h for h in range(n) if residual(h)]
+                viol = np.flatnonzero((flat != flat[want_idx.astype(np.int64)]).any(axis=1))
+                want = (bad_gates[0] if bad_gates else -1, int(viol[0]) if viol.size else -1)
+                info.update(what="planted copy violation", position=pos, want=want)
+                ok = self.w.circuit_check_dev(dw.ptr, dsel.ptr, dpub.ptr, didx.ptr, n) == want and set(bad_gates) <= {g}
+                ok = ok and (viol.size > 0 or int(want_idx[pos]) == pos)
+        finally:
+            for b in bufs:
+                b.free()
+        return bool(ok), info
+
+    def op_solve(self):
+        """plonk_circuit_solve_dev / plonk_circuit_solve_hints_dev on a random layered circuit whose number of rounds and width are drawn
+        here: the witness bit for bit and the level / evaluation counters against RefSolver / HintRefSolver; now and then a planted
+        dependency cycle (the smallest variable on it is reported), a definition the entry must refuse (and a good solve right after), and
+        the solved witness carried into preprocess_dev and plonk_circuit_check_dev, whose verdict must be the reference's: satisfied, or its
+        first unsatisfied gate (none without a planted constraint, unless a hinted inverse or quotient met a zero)."""
+        from distributed_plonk_amd import builder as BD
+        from distributed_plonk_amd import circuit as CI
+        from distributed_plonk_amd._ffi import PlonkError
+        from tests.circuit_cases import layered_circuit, ref_perm_idx
+        from tests.hint_ref import GIVEN, HintRefSolver
+        from tests.solve_ref import RefSolver
+        rs = self.rs
+        hints = bool(rs.randint(0, 2))
+        max_gates = 1 << min(self.max_log, 12)
+        widths = [x for x in (1, 63, 64, 65, 255, 256, 257) if 3 * x + 8 <= max_gates]
+        width = int(rs.choice(widths)) if rs.rand() < 0.8 else int(rs.randint(1, max(2, max_gates // 4)))
+        depth = int(rs.randint(1, 301))
+        planted = rs.rand() < 0.25
+        cseed = self.seed()
+        built, inputs, publics = layered_circuit(self.curve, depth, width, cseed, hints, max_gates, satisfied=not planted)
+        Ref = HintRefSolver if built.has_hints else RefSolver
+        info = dict(hints=hints, width=width, depth=depth, cseed=cseed, n=built.n, planted=planted)
+
+        def rebuilt(wire_vars=None, selector_evals=None, def_gate=None):
+            pick = lambda new, old: old.copy() if new is None else new
+            return BD.BuiltCircuit(built.curve, pick(wire_vars, built.wire_vars), pick(selector_evals, built.selector_evals), built.num_vars,
+                                   pick(def_gate, built.def_gate), built.input_vars, built.public_vars, built.zero_var, built.num_gates_unpadded,
+                                   hint_op=built.hint_op.copy())
+
+        ref = Ref(built, inputs, publics)
+        in_limbs, pub_limbs = ref.limbs(inputs), ref.limbs(publics)
+        defined = np.flatnonzero(built.def_gate != GIVEN)
+        defined = defined[defined >= 2]                               # not the zero and one gates
+        defined = np.array([v for v in defined if built.def_gate[v] >= built.num_public], dtype=np.int64)
+        pick_var = rs.rand()
+        try:
+            if pick_var < 0.125 and defined.size:                     # a dependency cycle x -> y -> x (or x -> x), x < y
+                cands = [v for v in defined[rs.permutation(defined.size)[:64]] if ref.live_wires(int(built.def_gate[v]))]
+                if cands:
+                    x = int(cands[0])
+                    gx = int(built.def_gate[x])
+                    users = [int(built.wire_vars[4, g]) for g in range(built.n)
+                             if int(built.def_gate[int(built.wire_vars[4, g])]) == g and int(built.wire_vars[4, g]) > x
+                             and any(int(built.wire_vars[i, g]) == x for i in ref.live_wires(g))]
+                    y = users[int(rs.randint(0, len(users)))] if users else x
+                    wv = built.wire_vars.copy()
+                    wv[ref.live_wires(gx)[0], gx] = y
+                    cyc = rebuilt(wire_vars=wv)
+                    info.update(what="cycle", x=x, y=y)
+                    try:
+                        cyc.solve_dev(self.w, in_limbs, pub_limbs).close()
+                        return False, info
+                    except CI.UnsolvableCircuit as ex:
+                        if ex.variable != x:
+                            info["reported"] = ex.variable
+                            return False, info
+                    finally:
+                        cyc.close()
+            elif pick_var < 0.25 and defined.size:                    # a definition the entry must refuse
+                v = int(defined[int(rs.randint(0, defined.size))])
+                g = int(built.def_gate[v])
+                kind = int(rs.randint(0, 3))
+                if kind == 0:
+                    dg = built.def_gate.copy()
+                    dg[v] = built.n + int(rs.randint(0, 3))
+                    bad, mentions = rebuilt(def_gate=dg), [f"variable {v}"]
+                elif kind == 1 and not (built.hint_op[g] & 0xFF):
+                    sel = built.selector_evals.copy()
+                    sel[10, g] = 0
+                    bad, mentions = rebuilt(selector_evals=sel), [f"variable {v}", "q_o"]
+                else:
+                    kind = 2
+                    wv = built.wire_vars.copy()
+                    i = int(rs.randint(0, 4))
+                    wv[i, g] = built.num_vars + int(rs.randint(0, 2))
+                    bad, mentions = rebuilt(wire_vars=wv), [f"wire {i}", f"gate {g}"]
+                info.update(what="refusal", variable=v, gate=g, kind=kind)
+                try:
+                    bad.solve_dev(self.w, in_limbs, pub_limbs).close()
+                    return False, info
+                except PlonkError as ex:
+                    if ex.code != -1:
+                        raise
+                    if not all(mt in str(ex) for mt in mentions):
+                        info["message"] = str(ex)[:200]
+                        return False, info
+                finally:
+                    bad.close()
+            # the solve itself: right after a cycle or a refusal on the same worker, or on its own
+            want, _ = ref.solve()
+            try:
+                s = built.solve_dev(self.w, in_limbs, pub_limbs)
+            except CI.UnsolvableCircuit as ex:                        # no cycle in this circuit: the reference has just solved it
+                info.update(what=info.get("what", "solve"), unsolvable=ex.variable)
+                return False, info
+            try:
+                info.setdefault("what", "solve")
+                ok = (np.array_equal(s.witness(), ref.limbs(want)) and s.levels == ref.depth()
+                      and s.evaluations == int((built.def_gate != GIVEN).sum()))
+                info.update(levels=int(s.levels))
+                if ok and rs.rand() < 0.5:
+                    unsat = ref.unsatisfied_gates(want)
+                    info.update(what=info["what"] + " + preprocess", first_unsatisfied=unsat[0] if unsat else -1)
+                    if (planted and not unsat) or (unsat and not planted and not built.has_hints):
+                        return False, info                            # the generator's own promise: unsatisfied exactly when planted (hints aside)
+                    try:
+                        inst = CI.preprocess_dev(self.w, s.d_wire_vars, built.n, built.num_vars, s.d_witness.ptr, s.d_selector_evals, s.d_pub.ptr,
+                                                 built.num_public, check=True)
+                        try:
+                            ok = not unsat and np.array_equal(inst.d_idx.download((5 * built.n,)), ref_perm_idx(built.wire_vars))
+                            ok = ok and np.array_equal(inst.d_wires.download((5, built.n, 4)), ref.limbs(want)[built.wire_vars.astype(np.int64)])
+                        finally:
+                            inst.close()
+                    except CI.UnsatisfiedCircuit as ex:
+                        ok = bool(unsat) and ex.gate == unsat[0] and ex.position == -1
+            finally:
+                s.close()
+        finally:
+            built.close()
+        return bool(ok), info
+
+    def op_rescue(self):
+        """plonk_rescue_permute_dev on `count` states and plonk_rescue_merkle_dev on a tree, both enqueued before either is read back, every
+        state and node against tests/rescue_ref.py; the parameters of each call by coin (rescue_params)."""
+        from distributed_plonk_amd import rescue as RS
+        from tests import rescue_ref as R
+        rs, p = self.rs, self.f.p
+        log_leaves = int(rs.randint(0, 8))
+        L = 1 << log_leaves
+        budget = 200 - (L - 1)                                        # reference permutations left for the states
+        count = int(rs.choice([c for c in (0, 1, 63, 64, 65) if c <= budget] + [int(rs.randint(0, min(200, budget) + 1))]))
+        prm_s, ref_s, name_s = self.rescue_params()
+        prm_t, ref_t, name_t = self.rescue_params()
+        states = self.fr(4 * count)
+        for _ in range(int(rs.randint(0, 4))):                       # 0, 1 and r - 1 in the states, a whole edge state now and then
+            if count:
+                states[4 * int(rs.randint(0, count)):][:4] = self.f.to_limbs(int(rs.choice([0, 1, -1])) % p)
+        leaves = self.fr(L)
+        info = dict(count=count, log_leaves=log_leaves, params=(name_s, name_t))
+        d_states, tree = self.up(states), None
+        try:
+            RS.permute_dev(self.w, prm_s, d_states.ptr, count)
+            tree = RS.MerkleTree(self.w, prm_t, leaves)
+            got_states = d_states.download((count, 4, 4)) if count else np.zeros((0, 4, 4), dtype=np.uint64)
+            got_nodes = tree.nodes
+        finally:
+            d_states.free()
+            if tree is not None:
+                tree.close()
+        si = self.ints(states)
+        want_states = [x for j in range(count) for x in R.permute(self.curve, si[4 * j:4 * j + 4], ref_s)]
+        info["what"] = "permute"
+        ok = self.ints(got_states) == want_states
+        if ok:
+            info["what"] = "merkle"
+            ok = got_nodes.shape == (2 * L - 1, 4) and self.ints(got_nodes) == R.merkle(self.curve, self.ints(leaves), ref_t)
+        return bool(ok), info
+
+    def acc_shape(self):
+        """(height, count) of an accumulator whose reference costs at most 200 permutations: chains of 1 to 40 links, 65 leaves across a wave,
+        ragged trees with every count mod 3"""
+        from tests import accumulator_ref as A
+        rs = self.rs
+        pick = rs.rand()
+        if pick < 0.25:                                               # a chain: one group, then height - 1 links
+            height, count = int(rs.randint(1, 41)), int(rs.randint(1, 4))
+        elif pick < 0.4:
+            height, count = int(rs.randint(4, 41)), 65
+        else:
+            height = int(rs.randint(1, 41))
+            count = int(rs.randint(1, min(3 ** min(height, 5), 120) + 1))
+        while sum(A.level_counts(height, count)) > 200:
+            count -= 1
+        return height, count
+
+    def acc_layout(self, levels, elems, uids):
+        """the (2 + 4 height) x m solver inputs, row-major, as residues, from the reference's paths"""
+        from tests import accumulator_ref as A
+        paths = [A.acc_path(levels, i) for i in uids]
+        vals = list(uids) + [elems[i] for i in uids]
+        for j in range(len(levels) - 1):
+            vals += [q[0][j] for q in paths] + [q[1][j] for q in paths] + [int(q[2][j] == 0) for q in paths] + [int(q[2][j] == 2) for q in paths]
+        return vals
+
+    def op_accumulator(self):
+        """plonk_rescue_acc_build_dev and plonk_rescue_acc_paths_dev: every node of every level, the level counts and offsets and the root against
+        tests/accumulator_ref.py, Accumulator.path for a few uids, the gathered solver inputs for a uid list with repeats in any order; a uid
+        >= count is refused naming the smallest offending index, and the same accumulator gathers correctly afterwards."""
+        from distributed_plonk_amd import rescue as RS
+        from distributed_plonk_amd._ffi import PlonkError
+        from tests import accumulator_ref as A
+        rs = self.rs
+        height, count = self.acc_shape()
+        prm, ref_prm, name = self.rescue_params()
+        elems = self.fr(count)
+        ei = self.ints(elems)
+        levels = A.acc_nodes(self.curve, height, ei, ref_prm)
+        info = dict(height=height, count=count, params=name)
+        acc = RS.Accumulator(self.w, prm, elems, height)
+        try:
+            info["what"] = "levels"
+            ok = (acc.level_counts == [len(l) for l in levels] == A.level_counts(height, count)
+                  and acc.level_offsets == [sum(acc.level_counts[:j]) for j in range(height + 1)] and acc.nodes.shape == (sum(len(l) for l in levels), 4))
+            ok = ok and all(self.ints(acc.level(j)) == want for j, want in enumerate(levels)) and self.ints(acc.root) == levels[-1]
+            if ok:
+                info["what"] = "path"
+                for i in sorted({0, count - 1, int(rs.randint(0, count))}):
+                    sib1, sib2, pos = acc.path(i)
+                    ok = ok and (self.ints(sib1), self.ints(sib2), pos) == A.acc_path(levels, i)
+            m = int(rs.randint(1, 9))
+            uids = [int(rs.randint(0, count)) for _ in range(m)]
+            if m > 2:
+                uids[1] = uids[0]                                     # a repeat
+            if ok and rs.rand() < 0.125:
+                bad = list(uids)
+                at = sorted(int(x) for x in rs.randint(0, m, size=int(rs.randint(1, 3))))
+                for i in at:
+                    bad[i] = count + int(rs.randint(0, 3))
+                info.update(what="refused uid", refused=bad)
+                try:
+                    acc.witness_inputs_dev(bad).free()
+                    ok = False
+                except PlonkError as ex:
+                    if ex.code != -1:
+                        raise
+                    ok = f"d_uids[{at[0]}]" in str(ex)
+            if ok:
+                info.update(what="gather" + (" after a refusal" if "refused" in info else ""), uids=uids)
+                buf = acc.witness_inputs_dev(uids)
+                try:
+                    got = buf.download(((2 + 4 * height) * m, 4))
+                finally:
+                    buf.free()
+                ok = self.ints(got) == self.acc_layout(levels, ei, uids)
+        finally:
+            acc.close()
+        return bool(ok), info
+
+    # -- the batched verifier
+    PROOF_SLOTS = [("wires_poly_comms", i) for i in range(5)] + [("prod_perm_poly_comm", None)] + [("split_quot_poly_comms", i) for i in range(5)] \
+        + [("opening_proof", None), ("shifted_opening_proof", None)]
+    PROOF_EVALS = [("wires_evals", i) for i in range(5)] + [("wire_sigma_evals", i) for i in range(4)] + [("perm_next_eval", None)]
+
+    @staticmethod
+    def proof_get(proof, slot):
+        name, i = slot
+        return proof[name] if i is None else proof[name][i]
+
+    @staticmethod
+    def proof_with(proof, slot, value):
+        name, i = slot
+        out = dict(proof)
+        if i is None:
+            out[name] = value
+        else:
+            out[name] = list(out[name])
+            out[name][i] = value
+        return out
+
+    def proved_instance(self):
+        """one small synthetic instance proved on this worker under the trapdoor key, kept for later draws; proved again when a coin says
+        so or when the worker's commit key was replaced since"""
+        from tests.circuit_cases import prove_synthetic
+        pr = self.proved
+        if pr is None or pr["key_epoch"] != self.key_epoch or self.rs.rand() < 0.2:
+            log_n = int(self.rs.randint(2, min(self.max_log, 6) + 1))
+            n_in = int(self.rs.randint(0, min(1 << log_n, 6) + 1))
+            tau = int.from_bytes(self.rs.bytes(31), "little") % self.f.p or 7
+            seed = self.seed()
+            vk, pub, proofs = prove_synthetic(self.w, self.O, self.cid, log_n, 2, seed, num_inputs=n_in, tau=tau)
+            self.n_bases = 0                                          # the instance installed its own commit key
+            self.proved = pr = dict(vk=vk, pub=pub, proofs=proofs, tau=tau, log_n=log_n, num_inputs=n_in, seed=seed, key_epoch=self.key_epoch)
+        return pr
+
+    def op_verify_batch(self):
+        """plonk_verify_batch_dev on a batch of K records filled from a pool of at most 8 distinct ones — the honest proof and mutants of it (an
+        evaluation + 1, two points swapped, a point negated, a point at (0, 0), a public input changed, a coordinate set to q, a point off
+        the curve): per lane the status word, with d_debug the six challenges, and verifier.batch_verify's verdict, against
+        oracle/verifier_ref.py evaluated once per distinct record."""
+        from distributed_plonk_amd import verifier as VF
+        from distributed_plonk_amd.transcript import FQ_MODULI, PlonkTranscript
+        from oracle import bigint_ref as B, verifier_ref as V
+        rs, f = self.rs, self.f
+        pr = self.proved_instance()
+        vk, pub0, tau = pr["vk"], np.asarray(pr["pub"], dtype=np.uint64).reshape(-1, 4), pr["tau"]
+        cv = B.CURVES[self.curve]
+        nq, q = VF._q64(self.curve), FQ_MODULI[self.curve]
+        honest = pr["proofs"][int(rs.randint(0, len(pr["proofs"])))]
+        info = dict(log_n=pr["log_n"], num_inputs=pr["num_inputs"], seed=pr["seed"])
+
+        def finite_slot():
+            for _ in range(32):
+                s = self.PROOF_SLOTS[int(rs.randint(0, 13))]
+                if not self.proof_get(honest, s)[1]:
+                    return s
+            return None
+
+        def mutant(kind):
+            """(public inputs, proof) or None where the kind does not apply"""
+            s = finite_slot()
+            if kind == "eval+1":
+                e = self.PROOF_EVALS[int(rs.randint(0, 10))]
+                return pub0, self.proof_with(honest, e, f.to_limbs((f.from_limbs(self.proof_get(honest, e)) + 1) % f.p))
+            if kind == "pub":
+                if not len(pub0):
+                    return None
+                pub = pub0.copy()
+                i = int(rs.randint(0, len(pub)))
+                pub[i] = f.to_limbs((f.from_limbs(pub[i]) + 1 + int(rs.randint(0, 1 << 30))) % f.p)
+                return pub, honest
+            if kind == "swap":
+                a, b = (self.PROOF_SLOTS[int(x)] for x in rs.permutation(13)[:2])
+                return pub0, self.proof_with(self.proof_with(honest, a, self.proof_get(honest, b)), b, self.proof_get(honest, a))
+            if kind == "zero":
+                return pub0, self.proof_with(honest, self.PROOF_SLOTS[int(rs.randint(0, 13))], (np.zeros(2 * nq, dtype=np.uint64), True))
+            if s is None:
+                return None
+            xy = np.array(self.proof_get(honest, s)[0], dtype=np.uint64).reshape(-1).copy()
+            if kind == "negate":
+                xy = VF._g1_neg(self.curve, xy)
+            elif kind == "coordinate=q":                              # the modulus itself in x or in y: not canonical
+                which = int(rs.randint(0, 2))
+                xy[which * nq:(which + 1) * nq] = [(q >> (64 * i)) & (2 ** 64 - 1) for i in range(nq)]
+            else:                                                     # off the curve: the low bits of x changed
+                xy[0] ^= np.uint64(1 + int(rs.randint(0, 255)))
+            return pub0, self.proof_with(honest, s, (xy, False))
+
+        def status_of(pub, proof):
+            """the status word by the rules of include/plonk_hip.h on Python integers: 8 for a coordinate >= q or a scalar >= r (such a point
+            is not looked at further), 1 for a finite canonical point off the curve"""
+            st = 0
+            for s in self.PROOF_SLOTS:
+                xy = VF._point_xy(self.curve, self.proof_get(proof, s))
+                x, y = (B.from_limbs([int(v) for v in xy[i * nq:(i + 1) * nq]]) for i in (0, 1))
+                if x >= q or y >= q:
+                    st |= 8
+                elif (x or y) and not B.on_curve(cv, (cv.fq.from_mont(x), cv.fq.from_mont(y))):
+                    st |= 1
+            for e in [self.proof_get(proof, e) for e in self.PROOF_EVALS] + list(pub):
+                if B.from_limbs([int(v) for v in e]) >= f.p:
+                    st |= 8
+            return st
+
+        kinds = ["eval+1", "swap", "negate", "zero", "pub", "coordinate=q", "off-curve"]
+        pool = {}                                                     # record bytes -> dict(pub, proof, kind, status, accept, ch)
+        def add(kind, rec):
+            if rec is None:
+                return
+            key = np.asarray(rec[0], dtype=np.uint64).tobytes() + VF.proof_record(self.curve, rec[1]).tobytes()
+            if key not in pool and len(pool) < 8:
+                pool[key] = dict(pub=rec[0], proof=rec[1], kind=kind)
+        add("honest", (pub0, honest))
+        for kind in [kinds[int(x)] for x in rs.permutation(len(kinds))[:int(rs.randint(1, 8))]]:
+            add(kind, mutant(kind))
+        recs = list(pool.values())
+        for r in recs:                                                # the reference, once per distinct record
+            r["status"] = status_of(r["pub"], r["proof"])
+            r["accept"], r["ch"] = False, None
+            if r["status"] == 0:
+                r["ch"] = V.derive_challenges(PlonkTranscript(self.curve), vk, list(r["pub"]), r["proof"])
+                try:
+                    V.verify(cv, vk, r["pub"], r["proof"], tau, challenges=r["ch"])
+                    r["accept"] = True
+                except V.VerificationError as ex:
+                    if "rejected" not in str(ex):                     # the statement itself is undefined: the reference cannot evaluate the record
+                        info.update(what="reference", kind=r["kind"], error=str(ex)[:120])
+                        return False, info
+        if not recs[0]["accept"]:
+            info.update(what="the reference rejects the honest proof")
+            return False, info
+        # lanes: malformed records cost nothing; a well-formed wrong one costs batch_verify's bisection about 2 log2 K host pairing checks, so few of them
+        K = int(rs.choice([1, 2, 63, 64, 65, 129, int(rs.randint(1, 201))]))
+        wrong = [i for i, r in enumerate(recs) if r["status"] == 0 and not r["accept"]]
+        free = [i for i, r in enumerate(recs) if r["status"] != 0]
+        lanes = [0] * K
+        for lane in range(K):
+            if free and rs.rand() < 0.3:
+                lanes[lane] = free[int(rs.randint(0, len(free)))]
+        for _ in range(min(len(wrong), 1 if K > 16 else 3)):
+            lanes[int(rs.choice([0, K - 1, 63 % K, 64 % K, int(rs.randint(0, K))]))] = wrong[int(rs.randint(0, len(wrong)))]
+        pubs, proofs = [recs[i]["pub"] for i in lanes], [recs[i]["proof"] for i in lanes]
+        info.update(K=K, pool=[r["kind"] for r in recs], lanes=lanes if K <= 16 else [(ln, i) for ln, i in enumerate(lanes) if i][:12])
+        rho = VF._rhos(self.curve, K, self.seed())
+        _, status, dbg = VF.device_verify(self.w, vk, pubs, proofs, rho, debug=True)
+        info["what"] = "status"
+        ok = [int(x) for x in status] == [recs[i]["status"] for i in lanes]
+        if ok:
+            info["what"] = "challenges"
+            for lane, i in enumerate(lanes):
+                ch = recs[i]["ch"]
+                want = np.zeros((6, 4), dtype=np.uint64) if ch is None else np.stack([ch[name] for name in ("beta", "gamma", "alpha", "zeta", "v", "u")])
+                ok = ok and np.array_equal(dbg[lane, :6], want)
+        if ok:
+            info["what"] = "verdict"
+            st = {}
+            verdict = VF.batch_verify(self.w, vk, VF.OpenKey.from_trapdoor(self.curve, tau), pubs, proofs, stats=st, _rho=rho)
+            ok = verdict == [recs[i]["accept"] for i in lanes] and st["status"] == [recs[i]["status"] for i in lanes]
+        return bool(ok), info
+
+    def op_membership(self):
+        """The whole chain on the dirty context: an accumulator of height <= 3 built on the device, m <= 2 memberships gathered there, the
+        membership circuit solved from the device inputs, preprocessed, proved, verified by the device verifier and by oracle/verifier_ref.py
+        under the trapdoor key; then the inputs spoiled in one way (a sibling swapped, a flag of 2, another uid, a wrong root), which
+        circuit.UnsatisfiedCircuit must refuse.  n <= 2^11."""
+        from distributed_plonk_amd import circuit as CI
+        from distributed_plonk_amd import rescue as RS
+        from distributed_plonk_amd import verifier as VF
+        from distributed_plonk_amd.membership import membership_circuit
+        from distributed_plonk_amd.prover import Prover
+        from distributed_plonk_amd.transcript import PlonkTranscript
+        from oracle import bigint_ref as B, verifier_ref as V
+        from tests import accumulator_ref as A
+        rs, f = self.rs, self.f
+        height, m = int(rs.randint(1, 4)), int(rs.randint(1, 3))
+        count = int(rs.randint(2, min(3 ** height, 12) + 1))
+        prm, ref_prm, name = self.rescue_params()
+        uids = [int(rs.randint(0, count)) for _ in range(m)]
+        tau = int.from_bytes(rs.bytes(31), "little") % f.p or 7
+        elems = self.fr(count)
+        info = dict(height=height, m=m, count=count, uids=uids, params=name)
+        key = (height, m, name == "default")
+        built = self.membership_built.get(key) if name == "default" else None
+        if built is None:
+            built = membership_circuit(self.curve, height, m, None if name == "default" else prm)
+            if name == "default":
+                self.membership_built[key] = built
+        n, rows = built.n, 2 + 4 * height
+        assert n <= 1 << 11, n
+        acc = RS.Accumulator(self.w, prm, elems, height)
+        d_in = ck = pv = inst = None
+        try:
+            root = acc.root.copy().reshape(1, 4)
+            info["what"] = "root"
+            ok = self.ints(root) == A.acc_nodes(self.curve, height, self.ints(elems), ref_prm)[-1]
+            d_in = acc.witness_inputs_dev(uids)
+            if ok:
+                info["what"] = "prove and verify"
+                try:
+                    inst = built.preprocess(self.w, public_inputs=root, check=True, d_inputs=d_in.ptr)
+                except CI.UnsatisfiedCircuit as ex:                   # the gathered inputs do not lead to the root
+                    info["unsatisfied"] = str(ex)[:120]
+                    return False, info
+                key_size = ((n + 3 + 31) >> 5) << 5
+                qb = 8 * 2 * VF._q64(self.curve)
+                ck = self.w.alloc(key_size * qb)
+                self.w.memset_dev(ck.ptr, 0, key_size * qb)
+                self.w.synth_srs(f.to_limbs(tau), n + 3, ck.ptr)
+                self.w.init_dev(ck.ptr, key_size, n, 8 * n)
+                self.n_bases = 0                                      # the next MSM operation installs its own SRS
+                pv = Prover(self.w, built.log_n)
+                pv.load_key_dev(inst.sel_ptrs, inst.sig_ptrs, inst.k)
+                pub = inst.public_inputs()
+                bl = dict(wires=self.O.rand_fr(self.cid, self.seed(), 10).reshape(5, 2, 4), perm=self.O.rand_fr(self.cid, self.seed(), 3))
+                proof = pv.prove_dev(inst.wev, inst.d_id.ptr, inst.d_idx.ptr, inst.d_pi.ptr, bl, pv.fiat_shamir(pub))
+                vk = pv.verifying_key()
+                ok = np.array_equal(pub, root) and VF.verify(self.w, vk, VF.OpenKey.from_trapdoor(self.curve, tau), pub, proof)
+                if ok:
+                    try:
+                        V.verify(B.CURVES[self.curve], vk, pub, proof, tau, transcript=PlonkTranscript(self.curve))
+                    except V.VerificationError as ex:
+                        ok, info["rejected"] = False, str(ex)[:200]
+            if ok:
+                good = d_in.download((rows * m, 4)).reshape(rows, m, 4)
+                bad, bad_root = good.copy(), root
+                col, lvl = int(rs.randint(0, m)), int(rs.randint(0, height))
+                spoil = str(rs.choice(["sibling swapped", "flag of 2", "another uid", "wrong root"]))
+                if spoil == "sibling swapped" and np.array_equal(good[2 + 4 * lvl, col], good[3 + 4 * lvl, col]):
+                    spoil = "flag of 2"                               # both siblings empty (0): swapping them changes nothing
+                if spoil == "sibling swapped":
+                    bad[2 + 4 * lvl, col], bad[3 + 4 * lvl, col] = good[3 + 4 * lvl, col], good[2 + 4 * lvl, col]
+                elif spoil == "flag of 2":
+                    bad[4 + 4 * lvl + int(rs.randint(0, 2)), col] = f.to_limbs(2)
+                elif spoil == "another uid":
+                    bad[0, col] = f.to_limbs((uids[col] + 1 + int(rs.randint(0, count))) % f.p)
+                else:
+                    bad_root = f.to_limbs((f.from_limbs(root[0]) + 1) % f.p).reshape(1, 4)
+                info.update(what="spoiled", spoil=spoil, column=col, level=lvl)
+                d_in.upload(bad)
+                try:
+                    built.preprocess(self.w, public_inputs=bad_root, check=True, d_inputs=d_in.ptr).close()
+                    ok = False
+                except CI.UnsatisfiedCircuit:
+                    pass
+        finally:
+            if pv is not None:
+                pv.close()
+            if inst is not None:
+                inst.close()
+            for b in (ck, d_in):
+                if b is not None:
+                    b.free()
+            acc.close()
+            if name != "default":
+                built.close()
+        return bool(ok), info
+
+    CORE_OPS = ["ntt", "coset_eval_interp", "msm", "commit_many", "poly", "lincomb", "perm_product", "transpose", "distributed_fft", "quotient", "compact_rows_fft", "round1", "prove_verify", "class_prove", "msm_table",
+                "perm_product_ranges", "class_ifft", "init_refuses_bad_srs", "trim"]
+    CIRCUIT_OPS = ["circuit_preprocess", "solve", "rescue", "accumulator", "verify_batch", "membership"]
+    OPS = CORE_OPS + CIRCUIT_OPS
+    GROUPS = {"core": CORE_OPS, "circuit": CIRCUIT_OPS}
 
     def close(self):
+        for built in self.membership_built.values():
+            built.close()
         self.w.close()
 
 
-def run(seconds, seed, curves, max_log, only=None, max_ops=None, verbose=True):
+def parse_ops(spec):
+    """--ops: operation names and the groups "core" (the MSM / NTT / prover side, nineteen operations) and "circuit" (circuits, witnesses,
+    Rescue trees, the verifier) -> the list that every draw indexes, in the order given, duplicates dropped"""
+    names = []
+    for part in (x.strip() for x in spec.split(",")):
+        for name in Fuzz.GROUPS.get(part, [part]):
+            if name not in Fuzz.OPS:
+                raise SystemExit(f"--ops: unknown operation or group {part!r} (groups: {', '.join(Fuzz.GROUPS)}; operations: {', '.join(Fuzz.OPS)})")
+            if name not in names:
+                names.append(name)
+    return names
+
+
+def run(seconds, seed, curves, max_log, only=None, max_ops=None, verbose=True, ops=None, trace=False):
+    ops = list(Fuzz.OPS) if ops is None else ops
     t_end = time.time() + seconds
     fz = [Fuzz(c, cid, seed + 1000 * cid, max_log) for c, cid in curves]
     counts = {}
@@ -626,10 +1290,12 @@ def run(seconds, seed, curves, max_log, only=None, max_ops=None, verbose=True):
     try:
         while time.time() < t_end and (max_ops is None or it < max_ops):
             f = fz[it % len(fz)]
-            name = only or Fuzz.OPS[int(f.rs.randint(0, len(Fuzz.OPS)))]
+            name = only or ops[int(f.rs.randint(0, len(ops)))]
             ok, info = getattr(f, "op_" + name)()
             counts[name] = counts.get(name, 0) + 1
             it += 1
+            if trace:
+                print(f"op {it} curve={f.curve} {name} {'ok' if ok else 'MISMATCH'} {info}", flush=True)
             if not ok:
                 print(f"MISMATCH curve={f.curve} op={name} iteration={it} seed={seed} params={info}", flush=True)
                 return 1, counts
@@ -648,9 +1314,11 @@ if __name__ == "__main__":
     ap.add_argument("--curve", default="both", choices=["bn254", "bls12_381", "both"])
     ap.add_argument("--max-log", type=int, default=13)
     ap.add_argument("--only", default=None, choices=Fuzz.OPS)
+    ap.add_argument("--ops", default=None, help="comma-separated operation names and groups (core, circuit) to draw from; default: all")
     ap.add_argument("--max-ops", type=int, default=None)
+    ap.add_argument("--trace", action="store_true", help="print every operation and its parameters as it finishes")
     a = ap.parse_args()
     cs = [("bn254", 0), ("bls12_381", 1)]
     if a.curve != "both":
         cs = [c for c in cs if c[0] == a.curve]
-    raise SystemExit(run(a.seconds, a.seed, cs, a.max_log, a.only, a.max_ops)[0])
+    raise SystemExit(run(a.seconds, a.seed, cs, a.max_log, a.only, a.max_ops, ops=None if a.ops is None else parse_ops(a.ops), trace=a.trace)[0])
