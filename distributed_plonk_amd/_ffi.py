@@ -59,6 +59,10 @@ EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_
 
 # name -> (restype, argtypes); every symbol include/plonk_hip.h declares
 PLONK_COMM_ID_BYTES = 128
+# the integers plonk_msm_plan fills, in the order of the PLONK_MSM_PLAN_* enum of include/plonk_hip.h
+MSM_PLAN_FIELDS = ("c", "W1", "G", "cb", "lp", "low_bits", "nblk", "idx_bits", "packed", "staged", "stage_cap", "fused_order", "nlev", "last_k", "gsplit",
+                   "heavy_thresh", "persistent", "grid_mode", "STAGE_MAX_CHUNKS", "STAGE_THREADS", "HEAVY_BUCKET", "HEAVY_SEGS", "SORT_SLICE_LOG", "n", "K",
+                   "n_cu", "acc_grid", "bin_shift")
 
 SIGNATURES = {
     "plonk_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
@@ -139,6 +143,7 @@ SIGNATURES = {
     "plonk_quotient_evals_class_dev": (C.c_int, [C.c_void_p, C.POINTER(QuotientInputs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                                  C.c_uint32, C.c_void_p]),
     "plonk_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
+    "plonk_msm_plan": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_int32), C.c_int]),
     "plonk_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "plonk_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "plonk_profile_get": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),

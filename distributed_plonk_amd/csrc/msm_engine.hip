@@ -1250,15 +1250,30 @@ static int plan_window(size_t n, int bits, int window_bits, const MsmTable& tab,
     return c;
 }
 
-// K >= 1 scalar vectors against the SAME bases in one set of launches (the independent commitments of a prover round): vector k
-// supplies the windows k*W1 .. (k+1)*W1 - 1 of one big (window, bucket) problem, so the sort, the bucket accumulation and the
-// reduction pyramid each run once over K times the work — no per-MSM launch gaps, wave tails or host round trips, which is what
-// bounds small MSMs (2^20 - 2^21 points per rank / per configs[1]).  lens[k] <= n valid scalars in vector k.
-template <int NQ>
-static int msm_slice(int curve, const BaseRec<NQ>* d_bases, const uint32_t* const* d_scalars, const size_t* lens, int K, bool scalars_mont,
-                     size_t n, XyzzPt<NQ>* h_result, MsmWorkspace& ws, int window_bits, const MsmTable& tab, hipStream_t stream) {
-    const FpParams<NQ>& P = fq_params<NQ>(curve);
-    const int bits = fr_params(curve).bits;
+// The plan of one launch set of msm_slice — n points, K scalar vectors against the same bases — as plain host arithmetic: no launch, no device
+// access (n_cu, the CU count of the device, is handed in; only `persistent` depends on it).  msm_slice consumes exactly this and plonk_msm_plan
+// reports it, so a test asserts the branch it means to run from what the engine decided (tests/msm_plans.py restates it in Python).
+struct MsmPlan {
+    int c, G, W1, W, cb, Wr;         // window bits, bucket sets and windows per vector, windows of the batch, log2 buckets per window, bucket sets
+    uint64_t nsub, nbuckets, max_heavy;
+    uint32_t heavy_thresh;
+    SetGeom sg;
+    SortGeom g;                      // stage_cap included
+    bool packed;                     // the level-1 scatter carries the partition in the entry's top bits (sort_scatter_kernel: ebits + lp <= 32)
+    uint64_t nhist, nscan_blocks;
+    int nlev;                        // reduction pyramid
+    uint64_t lev_n[16], lev_k[16], lev_nch[16], pyr;
+    uint32_t gsplit;                 // workgroups per (level, window) sum
+    bool grid_mode;
+    uint32_t g_logL, g_logH, g_nbits;
+    bool fused_order;                // effective: the bucket-size histogram rides in the level-2 sort
+    size_t lds_staged;
+    bool staged;                     // sort_partition_staged_kernel (else sort_partition_kernel)
+    uint32_t acc_grid;               // workgroups of the accumulation ...
+    bool persistent;                 // ... as persistent waves on a work counter
+};
+
+static int msm_plan(size_t n, int K, int bits, int window_bits, const MsmTable& tab, const MsmWorkspace& ws, int n_cu, MsmPlan& p) {
     int G = 1;
     const int c = plan_window(n, bits, window_bits, tab, &G);
     const int W1 = (bits + 1 + c - 1) / c;             // windows per scalar vector (signed digits: one spare bit for the last carry)
@@ -1288,9 +1303,124 @@ static int msm_slice(int curve, const BaseRec<NQ>* d_bases, const uint32_t* cons
         uint32_t ln = 1;
         while (((uint64_t)1 << ln) < (uint64_t)n) ln++;
         g.idx_bits = ((uint32_t)g.low_bits + 1 + ln <= 32) ? ln : 0;
+        if (ws.sort_slice_index) g.idx_bits = 0;       // "msm_sort_slice_index" (tests): the form of wide windows at huge n, valid at any size
     }
-    const uint64_t nhist = ((uint64_t)g.nreal + W) * g.nblk;
-    const uint64_t nscan_blocks = (nhist + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    p.c = c; p.G = G; p.W1 = W1; p.W = W; p.cb = cb; p.Wr = Wr;
+    p.nsub = nsub; p.nbuckets = nbuckets; p.heavy_thresh = heavy_thresh;
+    p.max_heavy = ((uint64_t)n * W) / heavy_thresh + 1;     // a bucket is heavy only above heavy_thresh entries
+    p.packed = (uint32_t)g.low_bits + SORT_SLICE_LOG + 1 + (uint32_t)g.lp <= 32;
+    p.nhist = ((uint64_t)g.nreal + W) * g.nblk;
+    p.nscan_blocks = (p.nhist + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    // reduction pyramid geometry
+    p.nlev = 0;
+    for (uint64_t cur = nb; cur > 1 && p.nlev < 15; p.nlev++) {
+        p.lev_n[p.nlev] = cur;
+        p.lev_k[p.nlev] = std::min<uint64_t>(REDUCE_K, cur);
+        p.lev_nch[p.nlev] = cur / p.lev_k[p.nlev];
+        cur = p.lev_nch[p.nlev];
+    }
+    p.pyr = 0;
+    for (int l = 0; l < p.nlev; l++) p.pyr += (uint64_t)Wr * p.lev_nch[l];
+    // plain mode: the per-(level, window) sums of large pyramids are split over `gsplit` workgroups and folded by a second launch
+    // (one workgroup per 2048 level-0 values: at 2^13 values per window — c = 16, the 2^20-point plan — a single workgroup walked 32 points per lane
+    //  before its 8-step tree, the deepest dependent chain of a small MSM's reduction)
+    p.gsplit = (uint32_t)std::min<uint64_t>(32, std::max<uint64_t>(1, (p.nlev ? p.lev_nch[0] : 1) / 2048));
+    // "msm_reduce_grid": buckets of a set as an H x L grid (5b); row / column sums in the limb form, then logL + 1 + logH bit sums per set
+    p.grid_mode = ws.reduce_grid != 0 && cb >= 2;
+    p.g_logL = (uint32_t)(cb + 1) / 2; p.g_logH = (uint32_t)cb - p.g_logL; p.g_nbits = p.g_logL + 1 + p.g_logH;
+    // the bucket-size histogram rides in the level-2 sort when a bucket is one sorted segment (no fixed-base table).  "msm_fused_order": 1 (default) = for
+    // launches of >= 2^23 points in total, where it takes 3 % off the commitment phase of a 2^24 step; below that the level-2 sort loses more to the
+    // histogram's atomics than the two saved launches give back (+0.7 % per 2^20 step; profiles/r05_msm_fused_order.txt); 2 = always (tests); 0 = never
+    p.fused_order = (ws.fused_order == 2 || (ws.fused_order == 1 && (uint64_t)n * (uint64_t)K >= ((uint64_t)1 << 23))) && sg.tab_stride == 0 && sg.G == sg.W1;
+    // the staged level-2 kernel: 78 KiB of LDS per workgroup (two per CU); what the counters and the slice starts leave is the staging buffer
+    const size_t lds_fixed = (((size_t)1 << g.low_bits) + (g.idx_bits ? 0 : g.nblk)) * 4;
+    p.lds_staged = 78 * 1024;
+    g.stage_cap = lds_fixed + 4096 * 4 <= p.lds_staged ? (uint32_t)((p.lds_staged - lds_fixed) / 4) : 0;
+    if (ws.sort_stage_cap > 0 && g.stage_cap) g.stage_cap = std::min<uint32_t>(g.stage_cap, std::max<uint32_t>((uint32_t)ws.sort_stage_cap, STAGE_THREADS));   // tests: force the chunked path
+    p.staged = g.low_bits >= 8 && g.stage_cap >= STAGE_THREADS && !getenv("PLONK_MSM_NO_STAGED_SORT");
+    // "msm_acc_persist" (default 4): the accumulation as that many workgroups per CU of persistent waves; 0 = one lane per bucket over the whole grid
+    p.acc_grid = (uint32_t)((nbuckets + 255) / 256);
+    p.persistent = false;
+    if (ws.acc_persist != 0) {
+        const uint32_t pgrid = ws.acc_persist > 0 ? (uint32_t)n_cu * (uint32_t)ws.acc_persist : (uint32_t)(-ws.acc_persist);   // < 0: absolute grid (tests)
+        if (pgrid < p.acc_grid) { p.persistent = true; p.acc_grid = pgrid; }      // small problems keep the plain grid
+    }
+    p.sg = sg; p.g = g;
+    return PLONK_OK;
+}
+
+// CU count of the CURRENT device, cached per device (a process may drive several GPUs from several threads)
+static int device_cu_count(int* out) {
+    static int cu_of_dev[64];
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    int n_cu = dev >= 0 && dev < 64 ? __atomic_load_n(&cu_of_dev[dev], __ATOMIC_ACQUIRE) : 0;
+    if (!n_cu) {
+        hipDeviceProp_t prop;
+        HIP_TRY(hipGetDeviceProperties(&prop, dev));
+        n_cu = std::max(prop.multiProcessorCount, 1);
+        if (dev >= 0 && dev < 64) __atomic_store_n(&cu_of_dev[dev], n_cu, __ATOMIC_RELEASE);
+    }
+    *out = n_cu;
+    return PLONK_OK;
+}
+
+// points per slice of an MSM ("msm_slice_log", default 2^26: workspace sizing) and scalar vectors per launch set for slices of m points: as far as
+// the 32-bit entry indices of the sort (m * W1 * K < 2^32), grid.y of the per-window launches and "msm_batch_max" allow
+static size_t msm_slice_points(const MsmWorkspace& ws) { return (size_t)1 << std::min(std::max(ws.slice_log, 8), 26); }
+static int msm_group(size_t m, int K, int bits, int window_bits, const MsmTable& tab, const MsmWorkspace& ws) {
+    int G_ = 1;
+    const int c = plan_window(m, bits, window_bits, tab, &G_);
+    const int W1 = (bits + 1 + c - 1) / c;
+    const uint64_t per = (uint64_t)m * W1;
+    int group = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)K, (0xfffffff0ull / per)));
+    if ((uint64_t)group * W1 > 65535) group = 65535 / W1;                    // grid.y of the per-window launches
+    return std::min(group, std::min(std::max(ws.batch_max, 1), 64));
+}
+
+// plonk_msm_plan: the plan of the FIRST launch set of an MSM of K vectors over n points (later sets of a sliced or grouped MSM differ only in
+// their point and vector counts), as the integers of include/plonk_hip.h (PLONK_MSM_PLAN_*).  The only device access is the CU count.
+int msm_plan_query(int curve, size_t n, int K, const MsmWorkspace& ws, int window_bits, const MsmTable& tab, int32_t* out, int n_out) {
+    if (n == 0 || K <= 0) return plonk_fail(PLONK_ERR_ARG, "msm plan: %zu points, %d vectors", n, K);
+    if (!out || n_out < PLONK_MSM_PLAN_FIELDS) return plonk_fail(PLONK_ERR_ARG, "msm plan: room for %d of %d fields", out ? n_out : 0, PLONK_MSM_PLAN_FIELDS);
+    const int bits = fr_params(curve).bits;
+    const size_t m = std::min(msm_slice_points(ws), n);
+    const int kn = std::min(msm_group(m, K, bits, window_bits, tab, ws), K);
+    int n_cu = 0;
+    int rc = device_cu_count(&n_cu);
+    if (rc) return rc;
+    MsmPlan p;
+    if ((rc = msm_plan(m, kn, bits, window_bits, tab, ws, n_cu, p))) return rc;
+    out[PLONK_MSM_PLAN_C] = p.c; out[PLONK_MSM_PLAN_W1] = p.W1; out[PLONK_MSM_PLAN_G] = p.G; out[PLONK_MSM_PLAN_CB] = p.cb;
+    out[PLONK_MSM_PLAN_LP] = p.g.lp; out[PLONK_MSM_PLAN_LOW_BITS] = p.g.low_bits; out[PLONK_MSM_PLAN_NBLK] = (int32_t)p.g.nblk;
+    out[PLONK_MSM_PLAN_IDX_BITS] = (int32_t)p.g.idx_bits; out[PLONK_MSM_PLAN_PACKED] = p.packed; out[PLONK_MSM_PLAN_STAGED] = p.staged;
+    out[PLONK_MSM_PLAN_STAGE_CAP] = (int32_t)p.g.stage_cap; out[PLONK_MSM_PLAN_FUSED_ORDER] = p.fused_order; out[PLONK_MSM_PLAN_NLEV] = p.nlev;
+    out[PLONK_MSM_PLAN_LAST_K] = p.nlev ? (int32_t)p.lev_k[p.nlev - 1] : 0; out[PLONK_MSM_PLAN_GSPLIT] = (int32_t)p.gsplit;
+    out[PLONK_MSM_PLAN_HEAVY_THRESH] = (int32_t)std::min<uint32_t>(p.heavy_thresh, 0x7fffffffu); out[PLONK_MSM_PLAN_PERSISTENT] = p.persistent;
+    out[PLONK_MSM_PLAN_GRID_MODE] = p.grid_mode; out[PLONK_MSM_PLAN_STAGE_MAX_CHUNKS] = (int32_t)STAGE_MAX_CHUNKS; out[PLONK_MSM_PLAN_STAGE_THREADS] = STAGE_THREADS;
+    out[PLONK_MSM_PLAN_HEAVY_BUCKET] = (int32_t)HEAVY_BUCKET; out[PLONK_MSM_PLAN_HEAVY_SEGS] = HEAVY_SEGS; out[PLONK_MSM_PLAN_SORT_SLICE_LOG] = SORT_SLICE_LOG;
+    out[PLONK_MSM_PLAN_N] = (int32_t)m; out[PLONK_MSM_PLAN_K] = kn; out[PLONK_MSM_PLAN_N_CU] = n_cu;
+    out[PLONK_MSM_PLAN_ACC_GRID] = (int32_t)std::min<uint32_t>(p.acc_grid, 0x7fffffffu); out[PLONK_MSM_PLAN_BIN_SHIFT] = (int32_t)p.sg.bin_shift;
+    return PLONK_OK;
+}
+
+// K >= 1 scalar vectors against the SAME bases in one set of launches (the independent commitments of a prover round): vector k
+// supplies the windows k*W1 .. (k+1)*W1 - 1 of one big (window, bucket) problem, so the sort, the bucket accumulation and the
+// reduction pyramid each run once over K times the work — no per-MSM launch gaps, wave tails or host round trips, which is what
+// bounds small MSMs (2^20 - 2^21 points per rank / per configs[1]).  lens[k] <= n valid scalars in vector k.
+template <int NQ>
+static int msm_slice(int curve, const BaseRec<NQ>* d_bases, const uint32_t* const* d_scalars, const size_t* lens, int K, bool scalars_mont,
+                     size_t n, XyzzPt<NQ>* h_result, MsmWorkspace& ws, int window_bits, const MsmTable& tab, hipStream_t stream) {
+    const FpParams<NQ>& P = fq_params<NQ>(curve);
+    int n_cu = 0;
+    if (ws.acc_persist != 0) { const int rc_cu = device_cu_count(&n_cu); if (rc_cu) return rc_cu; }
+    MsmPlan p;
+    { const int rc_plan = msm_plan(n, K, fr_params(curve).bits, window_bits, tab, ws, n_cu, p); if (rc_plan) return rc_plan; }
+    const int c = p.c, G = p.G, W1 = p.W1, W = p.W, cb = p.cb, Wr = p.Wr;
+    const uint64_t nsub = p.nsub, nbuckets = p.nbuckets, nhist = p.nhist, nscan_blocks = p.nscan_blocks;
+    const uint32_t heavy_thresh = p.heavy_thresh;
+    const SetGeom sg = p.sg;
+    const SortGeom g = p.g;
 
     size_t off = 0;
     const size_t o_dig = off; off = align_up(off + (size_t)n * W * 4, 256);
@@ -1304,34 +1434,21 @@ static int msm_slice(int curve, const BaseRec<NQ>* d_bases, const uint32_t* cons
     const size_t o_redo = off; off = align_up(off + (nbuckets + 1) * 4, 256);
     const size_t o_szh = off; off = align_up(off + 2 * SIZE_BINS * 4, 256);
     const size_t o_work = off; off = align_up(off + 4, 256);       // work counter of the persistent accumulation
-    const uint64_t max_heavy = ((uint64_t)n * W) / heavy_thresh + 1;     // a bucket is heavy only above heavy_thresh entries
+    const uint64_t max_heavy = p.max_heavy;
     const size_t o_heavy = off; off = align_up(off + (max_heavy + 1) * 4, 256);
     typedef XyzzL<LimbGeom<NQ>::NL, LimbGeom<NQ>::B> BucketL;
-    // reduction pyramid geometry
-    int nlev = 0;
-    uint64_t lev_n[16], lev_k[16], lev_nch[16];
-    for (uint64_t cur = nb; cur > 1 && nlev < 15; nlev++) {
-        lev_n[nlev] = cur;
-        lev_k[nlev] = std::min<uint64_t>(REDUCE_K, cur);
-        lev_nch[nlev] = cur / lev_k[nlev];
-        cur = lev_nch[nlev];
-    }
-    uint64_t pyr = 0;
-    for (int l = 0; l < nlev; l++) pyr += (uint64_t)Wr * lev_nch[l];
+    const int nlev = p.nlev;
+    const uint64_t *lev_n = p.lev_n, *lev_k = p.lev_k, *lev_nch = p.lev_nch, pyr = p.pyr;
     const size_t o_buckets = off; off = align_up(off + nbuckets * sizeof(BucketL), 256);
     const size_t o_acc = off; off = align_up(off + pyr * sizeof(BucketL), 256);
     const size_t o_sarr = off; off = align_up(off + pyr * sizeof(BucketL), 256);
     const uint32_t nsplit = 1;
-    // plain mode: the per-(level, window) sums of large pyramids are split over `gsplit` workgroups and folded by a second launch
-    // (one workgroup per 2048 level-0 values: at 2^13 values per window — c = 16, the 2^20-point plan — a single workgroup walked 32 points per lane
-    //  before its 8-step tree, the deepest dependent chain of a small MSM's reduction)
-    const uint32_t gsplit = (uint32_t)std::min<uint64_t>(32, std::max<uint64_t>(1, (nlev ? lev_nch[0] : 1) / 2048));
+    const uint32_t gsplit = p.gsplit;
     const size_t o_wsum = off; off = align_up(off + (size_t)Wr * (nlev + 1) * nsplit * sizeof(XyzzPt<NQ>), 256);
     const size_t o_wpart = off; off = align_up(off + (gsplit > 1 ? (size_t)Wr * (nlev + 1) * gsplit * sizeof(BucketL) : 0), 256);
     const size_t o_hpart = off; off = align_up(off + max_heavy * HEAVY_SEGS * sizeof(BucketL), 256);
-    // "msm_reduce_grid": buckets of a set as an H x L grid (5b); row / column sums in the limb form, then logL + 1 + logH bit sums per set
-    const bool grid_mode = ws.reduce_grid != 0 && cb >= 2;
-    const uint32_t g_logL = (uint32_t)(cb + 1) / 2, g_logH = (uint32_t)cb - g_logL, g_nbits = g_logL + 1 + g_logH;
+    const bool grid_mode = p.grid_mode;
+    const uint32_t g_logL = p.g_logL, g_logH = p.g_logH, g_nbits = p.g_nbits;
     const size_t o_grc = off; off = align_up(off + (grid_mode ? (size_t)Wr * (((size_t)1 << g_logL) + ((size_t)1 << g_logH)) * sizeof(BucketL) : 0), 256);
     const size_t o_gbits = off; off = align_up(off + (grid_mode ? (size_t)Wr * g_nbits * sizeof(XyzzPt<NQ>) : 0), 256);
     int rc = ensure_ws(ws, off);
@@ -1364,10 +1481,7 @@ static int msm_slice(int curve, const BaseRec<NQ>* d_bases, const uint32_t* cons
     for (int k = 0; k < K; k++)
         hipLaunchKernelGGL(msm_digits_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, d_scalars[k], (uint64_t)n, (uint64_t)lens[k], c, W1,
                            dig + (size_t)k * W1 * n, scalars_mont ? 1 : 0, fr_params(curve)); }
-    // the bucket-size histogram rides in the level-2 sort when a bucket is one sorted segment (no fixed-base table).  "msm_fused_order": 1 (default) = for
-    // launches of >= 2^23 points in total, where it takes 3 % off the commitment phase of a 2^24 step; below that the level-2 sort loses more to the
-    // histogram's atomics than the two saved launches give back (+0.7 % per 2^20 step; profiles/r05_msm_fused_order.txt); 2 = always (tests); 0 = never
-    const bool fused_order = (ws.fused_order == 2 || (ws.fused_order == 1 && (uint64_t)n * (uint64_t)K >= ((uint64_t)1 << 23))) && sg.tab_stride == 0 && sg.G == sg.W1;
+    const bool fused_order = p.fused_order;
     const SizeHist szh{fused_order ? ghist : nullptr, sg.bin_shift, (uint64_t)nbuckets};
     if (fused_order) HIP_TRY(hipMemsetAsync(ghist, 0, 2 * SIZE_BINS * 4, stream));
     { ProfScope ps("msm_sort", stream);
@@ -1381,12 +1495,8 @@ static int msm_slice(int curve, const BaseRec<NQ>* d_bases, const uint32_t* cons
     }
     hipLaunchKernelGGL(sort_scatter_kernel, dim3(g.nblk, W), dim3(SCATTER_THREADS), (2 * ((size_t)(1u << g.lp) + 1) + 1 + SORT_SLICE) * 4, stream, dig, g,
                        blk_off, tmp);
-    // the staged level-2 kernel: 78 KiB of LDS per workgroup (two per CU); what the counters and the slice starts leave is the staging buffer
-    const size_t lds_fixed = (((size_t)1 << g.low_bits) + (g.idx_bits ? 0 : g.nblk)) * 4;
-    const size_t lds_staged = 78 * 1024;
-    g.stage_cap = lds_fixed + 4096 * 4 <= lds_staged ? (uint32_t)((lds_staged - lds_fixed) / 4) : 0;
-    if (ws.sort_stage_cap > 0 && g.stage_cap) g.stage_cap = std::min<uint32_t>(g.stage_cap, std::max<uint32_t>((uint32_t)ws.sort_stage_cap, STAGE_THREADS));   // tests: force the chunked path
-    if (g.low_bits >= 8 && g.stage_cap >= STAGE_THREADS && !getenv("PLONK_MSM_NO_STAGED_SORT")) {
+    const size_t lds_staged = p.lds_staged;
+    if (p.staged) {
         static DeviceOnce attr2;
         HIP_TRY(attr2.run([] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&sort_partition_staged_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); }));
         hipLaunchKernelGGL(sort_partition_staged_kernel, dim3(g.nreal), dim3(STAGE_THREADS), lds_staged, stream, tmp, g, blk_off, sorted, offsets, szh);
@@ -1405,27 +1515,11 @@ static int msm_slice(int curve, const BaseRec<NQ>* d_bases, const uint32_t* cons
         hipLaunchKernelGGL(bucket_size_scan_kernel, dim3(1), dim3(SIZE_BINS), 0, stream, ghist, bin_cursor);
         hipLaunchKernelGGL(bucket_size_place_kernel, dim3(bgrid), dim3(256), 0, stream, offsets, nbuckets, sg, bin_cursor, order, (const uint32_t*)nullptr);
     } }
-    // "msm_acc_persist" (default 4): the accumulation as that many workgroups per CU of persistent waves; 0 = one lane per bucket over the whole grid
     uint32_t* work = nullptr;
-    uint32_t acc_grid = (uint32_t)((nbuckets + 255) / 256);
-    if (ws.acc_persist != 0) {
-        // CU count of the CURRENT device, cached per device (a process may drive several GPUs from several threads)
-        static int cu_of_dev[64];
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        int n_cu = dev >= 0 && dev < 64 ? __atomic_load_n(&cu_of_dev[dev], __ATOMIC_ACQUIRE) : 0;
-        if (!n_cu) {
-            hipDeviceProp_t prop;
-            HIP_TRY(hipGetDeviceProperties(&prop, dev));
-            n_cu = std::max(prop.multiProcessorCount, 1);
-            if (dev >= 0 && dev < 64) __atomic_store_n(&cu_of_dev[dev], n_cu, __ATOMIC_RELEASE);
-        }
-        const uint32_t pgrid = ws.acc_persist > 0 ? (uint32_t)n_cu * (uint32_t)ws.acc_persist : (uint32_t)(-ws.acc_persist);   // < 0: absolute grid (tests)
-        if (pgrid < acc_grid) {                                   // small problems keep the plain grid
-            work = (uint32_t*)(base + o_work);
-            HIP_TRY(hipMemsetAsync(work, 0, 4, stream));
-            acc_grid = pgrid;
-        }
+    const uint32_t acc_grid = p.acc_grid;
+    if (p.persistent) {
+        work = (uint32_t*)(base + o_work);
+        HIP_TRY(hipMemsetAsync(work, 0, 4, stream));
     }
     { ProfScope ps("msm_accumulate_kernel", stream);
     if (ws.fused_y3)
@@ -1550,18 +1644,11 @@ static int msm_run_t(int curve, const void* d_bases, const uint32_t* const* d_sc
                      MsmWorkspace& ws, int window_bits, const MsmTable& tab, hipStream_t stream) {
     const FpParams<NQ>& P = fq_params<NQ>(curve);
     std::vector<XyzzPt<NQ>> total((size_t)K, xyzz_inf<NQ>());
-    const size_t SLICE = (size_t)1 << std::min(std::max(ws.slice_log, 8), 26);      // default 2^26 points per slice (workspace sizing); "msm_slice_log" option for tests
+    const size_t SLICE = msm_slice_points(ws);      // default 2^26 points per slice (workspace sizing); "msm_slice_log" option for tests
     for (size_t s = 0; s < n; s += SLICE) {
         const size_t m = std::min(SLICE, n - s);
         // windows per vector for this slice size -> how many vectors fit one launch set
-        const int bits = fr_params(curve).bits;
-        int G_ = 1;
-        const int c = plan_window(m, bits, window_bits, tab, &G_);
-        const int W1 = (bits + 1 + c - 1) / c;
-        const uint64_t per = (uint64_t)m * W1;
-        int group = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)K, (0xfffffff0ull / per)));
-        if ((uint64_t)group * W1 > 65535) group = 65535 / W1;                    // grid.y of the per-window launches
-        group = std::min(group, std::min(std::max(ws.batch_max, 1), 64));
+        const int group = msm_group(m, K, fr_params(curve).bits, window_bits, tab, ws);
         for (int k0 = 0; k0 < K; k0 += group) {
             const int kn = std::min(group, K - k0);
             std::vector<const uint32_t*> ptrs(kn);

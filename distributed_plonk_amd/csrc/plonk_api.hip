@@ -255,6 +255,7 @@ extern "C" int plonk_set_option(plonk_ctx* ctx, const char* key, int64_t value) 
     if (!strcmp(key, "msm_fused_order")) { ctx->msm_ws.fused_order = value < 0 ? 0 : (value > 2 ? 2 : (int)value); return PLONK_OK; }   // 1 = large launches (default), 2 = always, 0 = never
     if (!strcmp(key, "msm_fused_y3")) { ctx->msm_ws.fused_y3 = value ? 1 : 0; return PLONK_OK; }      // default 1
     if (!strcmp(key, "msm_sort_stage_cap")) { ctx->msm_ws.sort_stage_cap = (int)std::max<int64_t>(0, value); return PLONK_OK; }   // tests: force the chunked level-2 sort
+    if (!strcmp(key, "msm_sort_slice_index")) { ctx->msm_ws.sort_slice_index = value ? 1 : 0; return PLONK_OK; }   // tests: slice-relative indices in the level-1 sort entries at any size
     if (!strcmp(key, "msm_acc_persist")) { ctx->msm_ws.acc_persist = (int)std::max<int64_t>(-65536, std::min<int64_t>(value, 8)); return PLONK_OK; }   // default 4; < 0: an absolute grid of -value workgroups (tests)
     if (!strcmp(key, "msm_reduce_grid")) { ctx->msm_ws.reduce_grid = value ? 1 : 0; return PLONK_OK; }   // experiment: grid reduction (msm_engine.hip, 5b); default 0
     if (!strcmp(key, "ntt_shoup")) {              // precomputed-quotient butterflies (ntt_kernels.hpp); the environment variable PLONK_NTT_NO_SHOUP only sets the initial value
@@ -264,6 +265,12 @@ extern "C" int plonk_set_option(plonk_ctx* ctx, const char* key, int64_t value) 
     if (!strcmp(key, "quotient_fuse")) { ctx->tables.quotient_fuse = (int)value; return PLONK_OK; }   // experiments, see quotient.hip
     if (!strcmp(key, "msm_slice_log")) { ctx->msm_ws.slice_log = (int)value; return PLONK_OK; }       // MSMs above 2^value points are sliced (8..26)
     return plonk_fail(PLONK_ERR_ARG, "plonk_set_option: unknown key %s", key);
+}
+
+// the plan msm_slice would run for K vectors over n points under this context's options: nothing is launched or allocated
+extern "C" int plonk_msm_plan(plonk_ctx* ctx, size_t n, int K, int32_t* out, int n_out) {
+    CHECK_CTX(ctx);
+    return msm_plan_query(ctx->curve, n, K, ctx->msm_ws, ctx->msm_window, ctx->msm_table, out, n_out);
 }
 
 extern "C" int plonk_last_kernel_ms(plonk_ctx* ctx, double* out_ms) {

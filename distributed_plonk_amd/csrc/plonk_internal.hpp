@@ -172,6 +172,7 @@ struct MsmWorkspace {
     int fused_order = 1;      // "msm_fused_order": the bucket-size histogram taken inside the level-2 sort and scanned inside the placement (round 5): 1 = for launches of >= 2^23 points, 2 = always, 0 = never
     int fused_y3 = 1;         // "msm_fused_y3": Y3 of the mixed addition under one Montgomery reduction (ec_lazy.hpp); 0 = two products
     int sort_stage_cap = 0;   // "msm_sort_stage_cap": > 0 caps the LDS staging buffer of the level-2 sort (entries; tests force its chunked path), 0 = what the LDS budget leaves
+    int sort_slice_index = 0; // "msm_sort_slice_index": 1 = level-1 sort entries carry the index within their 2^14-point slice at any size (idx_bits = 0; tests: the form that windows >= 19 bits take above 2^22 points)
     int reduce_grid = 0;      // "msm_reduce_grid": 1 = the window reduction as row / column tree sums + bit sums (msm_grid_sums_kernel) instead of the running-sum pyramid; experiment, not measured yet
     int acc_persist = 4;      // "msm_acc_persist": workgroups per CU of the persistent bucket accumulation (0 = one lane per bucket over the whole grid; < 0: an absolute grid of that many workgroups, for tests)
 };
@@ -195,6 +196,8 @@ int msm_run(int curve, const void* d_bases, const uint32_t* d_scalars, bool scal
 // K scalar vectors (lens[k] valid entries, zero beyond) against the same bases[0 .. n): h_out_jac receives K Jacobian triples.
 int msm_run_many(int curve, const void* d_bases, const uint32_t* const* d_scalars, const size_t* lens, int K, bool scalars_mont, size_t n,
                  uint32_t* h_out_jac, MsmWorkspace& ws, int window_bits, const MsmTable& tab, hipStream_t stream);
+// the plan of the first launch set of an MSM of K vectors over n points under the options in ws: PLONK_MSM_PLAN_FIELDS integers (include/plonk_hip.h)
+int msm_plan_query(int curve, size_t n, int K, const MsmWorkspace& ws, int window_bits, const MsmTable& tab, int32_t* out, int n_out);
 int msm_table_plan(int curve, size_t n, int mode, size_t budget_bytes, int force_c, int force_sets, int* W_out, int* G_out, int* T_out);
 int msm_table_build(int curve, void* d_table, size_t n, size_t stride, int shift, int T, hipStream_t stream);
 int msm_jac_add_host(int curve, const uint32_t* a, const uint32_t* b, uint32_t* out);

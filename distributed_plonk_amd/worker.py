@@ -466,6 +466,13 @@ class PlonkWorker:
     def set_option(self, key: str, value: int):
         check(self.lib.plonk_set_option(self.ctx, key.encode(), value))
 
+    def msm_plan(self, n: int, K: int = 1) -> dict:
+        """The plan the MSM engine would run for K scalar vectors over n points under the current options (plonk_msm_plan; nothing is
+        launched): the PLONK_MSM_PLAN_* integers of include/plonk_hip.h by name."""
+        out = (C.c_int32 * len(_ffi.MSM_PLAN_FIELDS))()
+        check(self.lib.plonk_msm_plan(self.ctx, n, K, out, len(out)))
+        return dict(zip(_ffi.MSM_PLAN_FIELDS, out))
+
     def sync(self):
         check(self.lib.plonk_sync(self.ctx))
 

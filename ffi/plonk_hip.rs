@@ -28,6 +28,8 @@ pub const PLONK_ERR_HIP: c_int = -3;
 pub const PLONK_ERR_STATE: c_int = -4;
 pub const PLONK_ERR_EXCHANGE: c_int = -5;
 pub const PLONK_COMM_ID_BYTES: usize = 128;
+/// integers filled by `plonk_msm_plan` (the PLONK_MSM_PLAN_* enum of include/plonk_hip.h)
+pub const PLONK_MSM_PLAN_FIELDS: usize = 28;
 
 /// utils.rs:3-8 / hello_world.capnp:8-13
 #[repr(C)]
@@ -176,6 +178,7 @@ extern "C" {
     pub fn plonk_init_dev(ctx: *mut plonk_ctx, d_bases_xy: *const c_void, n_bases: usize, domain_size: usize, quot_domain_size: usize) -> c_int;
     pub fn plonk_debug_field_op(ctx: *mut plonk_ctx, field: c_int, op: c_int, a: *const u64, b: *const u64, out: *mut u64, n: usize) -> c_int;
     pub fn plonk_set_option(ctx: *mut plonk_ctx, key: *const c_char, value: i64) -> c_int;
+    pub fn plonk_msm_plan(ctx: *mut plonk_ctx, n: usize, k: c_int, out: *mut i32, n_out: c_int) -> c_int;
     pub fn plonk_last_kernel_ms(ctx: *mut plonk_ctx, out_ms: *mut f64) -> c_int;
     pub fn plonk_profile_enable(ctx: *mut plonk_ctx, on: c_int) -> c_int;
     pub fn plonk_profile_reset(ctx: *mut plonk_ctx) -> c_int;

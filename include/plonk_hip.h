@@ -466,13 +466,51 @@ int plonk_debug_field_op(plonk_ctx* ctx, int field, int op, const uint64_t* a, c
  * "msm_precompute" (fixed-base window table built at the next init: 0 off = default, 1 when the cost model predicts a gain, 2 whenever a usable
  * shape exists — a pinned width that is unusable for the SRS at hand falls back to no table, never to an error),
  * "msm_table_c" (0 or 4..21) / "msm_table_sets" / "msm_table_budget_mib" (the table's window width, bucket sets per scalar and memory budget;
- * 0 = the plan's choice), "msm_sort_stage_cap" (tests: caps the LDS staging buffer of the level-2 sort), "msm_reduce_grid" (default 0: the window
+ * 0 = the plan's choice), "msm_sort_stage_cap" (tests: caps the LDS staging buffer of the level-2 sort), "msm_sort_slice_index" (tests, default 0:
+ * 1 = the level-1 sort entries carry the index within their 2^14-point slice at any size, the form that otherwise needs wide windows above 2^22
+ * points), "msm_reduce_grid" (default 0: the window
  * reduction as tree sums over the bucket grid instead of the running-sum pyramid — faster for one small MSM alone, not beside another context's
  * accumulation: profiles/r04_pin_nop_experiment.txt), "msm_fused_order" (the bucket-size histogram inside the level-2 sort: 1 = for launches of
  * >= 2^23 points (default), 2 = always, 0 = never), "msm_fused_y3", "ntt_shoup" (both curves, default 1: precomputed-quotient butterflies in
  * the NTT passes; 0 = Montgomery butterflies), "check_bases" (default 1: plonk_init* verifies that every base is a curve point), "quotient_fuse" (6 = default: the compact kernel; 0-5, 7: other formulations).
  * INTEGRATION.md §6 has the table. */
 int plonk_set_option(plonk_ctx* ctx, const char* key, int64_t value);
+/* The plan the MSM engine would run for K scalar vectors over n points under this context's options (window, table, the msm_* knobs): the host-side
+ * choices of kernels and layouts, computed by the function the engine itself consumes.  Nothing is launched or allocated.  An MSM above the slice
+ * size or the batching limits runs as several launch sets; the plan is that of the first (PLONK_MSM_PLAN_N points, PLONK_MSM_PLAN_K vectors).
+ * out receives PLONK_MSM_PLAN_FIELDS integers (n_out >= that); PLONK_ERR_ARG where the engine would refuse the MSM. */
+enum {
+    PLONK_MSM_PLAN_C = 0,            /* window bits */
+    PLONK_MSM_PLAN_W1,               /* windows per scalar vector */
+    PLONK_MSM_PLAN_G,                /* bucket sets per scalar vector (= W1 without a fixed-base table) */
+    PLONK_MSM_PLAN_CB,               /* log2 buckets per window = c - 1 */
+    PLONK_MSM_PLAN_LP,               /* log2 level-1 partitions per window */
+    PLONK_MSM_PLAN_LOW_BITS,         /* log2 buckets per partition = cb - lp */
+    PLONK_MSM_PLAN_NBLK,             /* 2^SORT_SLICE_LOG-point slices per window */
+    PLONK_MSM_PLAN_IDX_BITS,         /* bits of the point index in a level-1 entry; 0 = index within the slice, slice recovered by search */
+    PLONK_MSM_PLAN_PACKED,           /* 1 = the level-1 scatter carries the partition in the entry (low_bits + SORT_SLICE_LOG + 1 + lp <= 32) */
+    PLONK_MSM_PLAN_STAGED,           /* 1 = LDS-staged level-2 kernel, 0 = direct */
+    PLONK_MSM_PLAN_STAGE_CAP,        /* entries of the staging buffer (also reported when the direct kernel runs) */
+    PLONK_MSM_PLAN_FUSED_ORDER,      /* 1 = the bucket-size histogram is taken inside the level-2 sort (effective, not the option) */
+    PLONK_MSM_PLAN_NLEV,             /* levels of the reduction pyramid */
+    PLONK_MSM_PLAN_LAST_K,           /* inputs per chunk of the last level (2 for odd cb, else 4; 0 without levels) */
+    PLONK_MSM_PLAN_GSPLIT,           /* workgroups per (level, window) sum; > 1 adds the fold launch */
+    PLONK_MSM_PLAN_HEAVY_THRESH,     /* entries above which a bucket goes to the heavy kernel */
+    PLONK_MSM_PLAN_PERSISTENT,       /* 1 = accumulation as persistent waves on a work counter (depends on the device's CU count) */
+    PLONK_MSM_PLAN_GRID_MODE,        /* 1 = grid reduction instead of the pyramid */
+    PLONK_MSM_PLAN_STAGE_MAX_CHUNKS, /* kernel constants the data-dependent choices rest on ... */
+    PLONK_MSM_PLAN_STAGE_THREADS,
+    PLONK_MSM_PLAN_HEAVY_BUCKET,
+    PLONK_MSM_PLAN_HEAVY_SEGS,
+    PLONK_MSM_PLAN_SORT_SLICE_LOG,
+    PLONK_MSM_PLAN_N,                /* points of the (first) launch set */
+    PLONK_MSM_PLAN_K,                /* scalar vectors of the (first) launch set */
+    PLONK_MSM_PLAN_N_CU,             /* CUs of the current device */
+    PLONK_MSM_PLAN_ACC_GRID,         /* workgroups of the accumulation */
+    PLONK_MSM_PLAN_BIN_SHIFT,        /* resolution of the bucket-size bins */
+    PLONK_MSM_PLAN_FIELDS
+};
+int plonk_msm_plan(plonk_ctx* ctx, size_t n, int K, int32_t* out, int n_out);
 /* Timing of the kernels launched by the last plonk_*_dev call on this context, measured with HIP
  * events on the context's stream (milliseconds). */
 int plonk_last_kernel_ms(plonk_ctx* ctx, double* out_ms);

@@ -219,6 +219,37 @@ def test_host_side_point_functions_match_the_oracle(curve):
     assert same(add(acc_l, acc_l), O.jac_add(curve, acc_o, acc_o))               # doubling of a non-normalised point
 
 
+def test_msm_digit_restatement_recomposes_the_scalar_and_feeds_the_chunk_rule():
+    """tests/msm_plans.py without a device: the signed digits stand for the scalar they were cut from (every width the engine allows, both
+    scalar sizes, the carry into the spare top window), the partition lengths count the non-zero digits, and the chunk rule of the staged
+    level-2 sort gives one chunk up to the buffer, 3/4-full chunks above it and the direct path beyond STAGE_MAX_CHUNKS."""
+    import msm_plans as M
+    from oracle import oracle as O
+    for cid in (0, 1):
+        sc = O.from_mont(cid, O.rand_fr(cid, 17, 64)).copy()
+        sc[0] = 0
+        sc[1] = [1, 0, 0, 0]
+        sc[2] = O.field_const(cid, 0, 0) - np.array([1, 0, 0, 0], dtype=np.uint64)
+        ints = [int.from_bytes(s.tobytes(), "little") for s in sc]
+        for c in range(2, 21):
+            p = M.plan(M.FR_BITS[cid], 64, 1, c)
+            dig = M.signed_digits(sc, c, p["W1"])
+            assert int((dig & np.uint32(0x7fffffff)).max()) <= 1 << (c - 1)
+            assert M.digits_value(dig, c) == ints, (cid, c)
+            assert M.partition_lengths(dig, p).sum() == np.count_nonzero(dig & np.uint32(0x7fffffff))
+    p = M.plan(254, 1 << 13, 1, 20, {"msm_sort_stage_cap": 2048})
+    assert (p["stage_cap"], p["low_bits"], p["staged"]) == (2048, 9, 1)
+    assert M.chunks(2048, p) == (1, False, 512) and M.chunks(2049, p) == (2, False, 256) and M.chunks(8192, p) == (6, False, 86)
+    assert M.chunks(8 * 1536, p) == (8, False, 64) and M.chunks(8 * 1536 + 1, p) == (1, True, 512)
+    counts = np.full(512, 8)
+    counts[259] += 4096
+    assert [s for _, s in M.chunk_entries(counts, p)] == [True, True, True, False, True, True]
+    ids = [r["id"] for r in M.PLAN_CASES]
+    assert len(set(ids)) == len(ids) and all(set(r["branches"]) <= set(M.FEATURES) for r in M.PLAN_CASES)
+    # every required branch is named by some row (whether the row REACHES it is judged from the engine's plan: tests/test_gpu_msm_plans.py)
+    assert M.missing_branches(M.PLAN_CASES, lambda r, f: True) == []
+
+
 def test_forced_plan_list_covers_every_pass_shape():
     """tests/ntt_plans.py, the planner as the forced-plan GPU tests restate it, on their list of (ntt_max_log_r, log size): widths 2 ... 7 in
     every position of a three-pass plan, the four-pass plans, and the plans the list was chosen for"""

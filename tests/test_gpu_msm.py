@@ -243,10 +243,11 @@ def test_persistent_accumulation_matches_plain_grid_and_oracle(gpu_workers, orac
 
 @pytest.mark.parametrize("curve,cid", [("bn254", 0), ("bls12_381", 1)])
 def test_bucket_ordering_fused_into_the_sort_matches_the_three_launch_form(gpu_workers, oracle, curve, cid):
-    """`msm_fused_order` (round 5): the bucket-size histogram taken inside the level-2 sort — both partition kernels: the direct one (narrow
-    windows) and the LDS-staged one (2^8 and more buckets per partition), its chunked path included — and scanned inside the placement.  The
-    default switches it on from 2^23 points per launch only, so it is FORCED here (2) against the three-launch form (0) and the oracle, with
-    duplicated bases, an infinity base, a heavy bucket and a batched round."""
+    """`msm_fused_order` (round 5): the bucket-size histogram taken inside the level-2 sort and scanned inside the placement.  The default
+    switches it on from 2^23 points per launch only, so it is FORCED here (2) against the three-launch form (0) and the oracle, with duplicated
+    bases, an infinity base, a heavy bucket and a batched round.  Every case here runs the DIRECT partition kernel: c = 14 has 2^3 buckets per
+    partition (low_bits = 3) and the LDS-staged kernel starts at 2^8 (c >= 19), so a stage cap has no effect on it; the staged kernel, its
+    chunks and its per-chunk direct path are forced with this option in tests/test_gpu_msm_plans.py."""
     w = gpu_workers(curve)
     n = 1 << 13
     bases = oracle.gen_bases(cid, 33, 300, n)
@@ -255,7 +256,7 @@ def test_bucket_ordering_fused_into_the_sort_matches_the_three_launch_form(gpu_w
     rnd = oracle.from_mont(cid, oracle.rand_fr(cid, 34, n))
     same = np.repeat(rnd[:1], n, axis=0)
     try:
-        for name, sc, window, cap in (("uniform", rnd, 0, 0), ("c5-direct-sort", rnd, 5, 0), ("c14-staged-sort", rnd, 14, 0), ("c14-chunked", rnd, 14, 1024),
+        for name, sc, window, cap in (("uniform", rnd, 0, 0), ("c5-direct-sort", rnd, 5, 0), ("c14-direct-low3", rnd, 14, 0), ("c14-direct-low3-cap-ignored", rnd, 14, 1024),
                                       ("all-equal", same, 0, 0)):
             w.set_option("msm_window", window)
             w.set_option("msm_sort_stage_cap", cap)

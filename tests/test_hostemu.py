@@ -33,7 +33,7 @@ def emu_env():
     return env
 
 
-def _pytest(env, files, k=None, timeout=900, extra_env=None):
+def _run_gpu_tests(env, files, k=None, timeout=900, extra_env=None):
     e = dict(env)
     e.update(extra_env or {})
     cmd = [sys.executable, "-m", "pytest", "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider", *files]
@@ -62,39 +62,47 @@ def test_smoke_entry_point(emu_env):
 def test_field_ntt_golden_quotient_kernels(emu_env):
     """test_gpu_ntt.py includes the plans forced with option ntt_max_log_r (every pass shape the planner can produce, four-pass plans, the
     refusal of a fifth pass), up to 2^21 points"""
-    _pytest(emu_env, ["tests/test_gpu_field.py", "tests/test_gpu_ntt.py", "tests/test_gpu_golden.py", "tests/test_gpu_quotient.py"])
+    _run_gpu_tests(emu_env, ["tests/test_gpu_field.py", "tests/test_gpu_ntt.py", "tests/test_gpu_golden.py", "tests/test_gpu_quotient.py"])
 
 
 def test_msm_kernels(emu_env):
     # every MSM parity test but the forced chunked level-2 sort (40 s of CPU); the persistent accumulation, redo / heavy paths,
     # forced windows, sharded MSMs and commit / round1 are in
-    _pytest(emu_env, ["tests/test_gpu_msm.py"], k="not level2_sort_in_chunks")
+    _run_gpu_tests(emu_env, ["tests/test_gpu_msm.py"], k="not level2_sort_in_chunks")
+
+
+def test_msm_plan_restatement_case_table_and_narrow_cases(emu_env):
+    """tests/test_gpu_msm_plans.py: the planner restated in tests/msm_plans.py against plonk_msm_plan for every window, size up to 2^26 and option
+    (the query launches nothing), every row of PLAN_CASES reaching the branches it names, and the narrow rows (windows up to 15 bits, 2^12
+    points) computed; the wide windows stay with the GPU (a c = 20 reduction walks 7 million buckets)."""
+    out = _run_gpu_tests(emu_env, ["tests/test_gpu_msm_plans.py"], k="restatement or case_table or emu")
+    assert "20 passed" in out, out
 
 
 def test_poly_kernels(emu_env):
-    _pytest(emu_env, ["tests/test_gpu_polyops.py"], k="not valid_permutation_closes and not full_size")
+    _run_gpu_tests(emu_env, ["tests/test_gpu_polyops.py"], k="not valid_permutation_closes and not full_size")
 
 
 def test_prover_and_verifier_on_emulated_device(emu_env):
     """The five rounds on the (emulated) device against the oracle prover, and device proofs accepted by the trapdoor verifier."""
-    _pytest(emu_env, ["tests/test_gpu_prover.py"], k="rounds_match_oracle and (3-False or 6-True) or real_transcript and bn254 or rejects_unsatisfied "
+    _run_gpu_tests(emu_env, ["tests/test_gpu_prover.py"], k="rounds_match_oracle and (3-False or 6-True) or real_transcript and bn254 or rejects_unsatisfied "
                                                      "or six_coset and 4-False-bn254")
-    _pytest(emu_env, ["tests/test_gpu_verifier.py"], k="synthetic_circuits and (4-coset8n-bn254 or 5-classes6-bn254) or oracle_circuit or trapdoor_key and bn254 "
+    _run_gpu_tests(emu_env, ["tests/test_gpu_verifier.py"], k="synthetic_circuits and (4-coset8n-bn254 or 5-classes6-bn254) or oracle_circuit or trapdoor_key and bn254 "
                                                        "or unsatisfied")
 
 
 def test_class_prover_ranks_as_threads(emu_env):
-    _pytest(emu_env, ["tests/test_gpu_class_prover.py"], k="matches_oracle and 4-2-bn254 or sharded_commit_key and 5-2-bn254 or in_library_rccl or failure_in_one_gate_range")
+    _run_gpu_tests(emu_env, ["tests/test_gpu_class_prover.py"], k="matches_oracle and 4-2-bn254 or sharded_commit_key and 5-2-bn254 or in_library_rccl or failure_in_one_gate_range")
 
 
 def test_rank_programs_as_processes_world_2_and_4(emu_env):
     """tests/test_gpu_multirank.py's rank programs — RankProver.fft_dev in all four modes at n and 8n on two contexts, the zero-padded row
     pass, a round of sharded commitments through the point all-gather, and the whole ClassProver with a sharded key, the transcript
     on every rank and the verifier on rank 0 — one process per rank through plonk_comm_*."""
-    out = _pytest(emu_env, ["tests/test_gpu_multirank.py"], k="bn254 and (2] or 9-4])", extra_env={"HIPEMU_THREADS": "2"})
+    out = _run_gpu_tests(emu_env, ["tests/test_gpu_multirank.py"], k="bn254 and (2] or 9-4])", extra_env={"HIPEMU_THREADS": "2"})
     assert "3 passed" in out, out
     # collectives entered on different communicators / of different kinds on different ranks: refused on every rank, nothing hangs (world 2 and 4)
-    out = _pytest(emu_env, ["tests/test_gpu_multirank.py"], k="different_orders and (2] or 4])", extra_env={"HIPEMU_THREADS": "2"}, timeout=600)
+    out = _run_gpu_tests(emu_env, ["tests/test_gpu_multirank.py"], k="different_orders and (2] or 4])", extra_env={"HIPEMU_THREADS": "2"}, timeout=600)
     assert "2 passed" in out, out
 
 
@@ -102,13 +110,13 @@ def test_distributed_transform_steps_and_coset_classes(emu_env):
     """fft_init / fft1 / fft2_prepare / fft2 per step against the oracle's helpers, S = 1, 2, 4 workloads in one process, the zero-padded row
     pass up to 2^19, call-order errors; the zero-padding-aware coset FFT for every class count, also under forced plans with first passes
     of width 3 and 4 (the 2^20 + 3 case and the full-size cross-check stay with the GPU)."""
-    _pytest(emu_env, ["tests/test_gpu_distributed.py"], k="not (25-2 or 24-4 or 22-2 or rccl or two_contexts)")
-    _pytest(emu_env, ["tests/test_gpu_coset_classes.py"], k="not full_size and not 1048579")
+    _run_gpu_tests(emu_env, ["tests/test_gpu_distributed.py"], k="not (25-2 or 24-4 or 22-2 or rccl or two_contexts)")
+    _run_gpu_tests(emu_env, ["tests/test_gpu_coset_classes.py"], k="not full_size and not 1048579")
 
 
 def test_batched_commitments_and_fixed_base_table(emu_env):
-    _pytest(emu_env, ["tests/test_gpu_commit_many.py"], k="not full_size and not group_limit")
-    _pytest(emu_env, ["tests/test_gpu_msm_table.py"], k="bn254")
+    _run_gpu_tests(emu_env, ["tests/test_gpu_commit_many.py"], k="not full_size and not group_limit")
+    _run_gpu_tests(emu_env, ["tests/test_gpu_msm_table.py"], k="bn254")
 
 
 def test_compiled_cpp_host_program(emu_env, tmp_path):
