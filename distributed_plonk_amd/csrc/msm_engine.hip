@@ -5,12 +5,17 @@
 // and src/dispatcher2.rs:835-893.  Only the group element is contractual
 // (Appendix A.1), so the GPU algorithm is free to differ from the CPU one:
 //
-//   1. digits      every scalar is cut into W = ceil((bits+1)/c) SIGNED c-bit digits, stored planar
-//                                                                              (msm_digits_kernel)
-//   2/3. sort      two-level LDS-staged counting sort of the (window, |digit|) keys: per-slice partition
-//                  histograms + one exclusive scan, a coalesced level-1 scatter, then one workgroup per
-//                  partition orders its L2-resident entries and emits the bucket offsets
-//                                                           (sort_hist / scan_* / sort_scatter / sort_partition)
+//   1/2. level 1   ONE pass over the scalars: every scalar leaves Montgomery form once and is cut into W = ceil((bits+1)/c) SIGNED c-bit
+//                  digits, stored planar, and the same lanes count the per-(slice, window) partition histograms in LDS
+//                                                                              (sort_digits_hist_kernel; scan_* turns counts into ranges)
+//   3. sort        two-level LDS-staged counting sort of the (window, |digit|) keys: the level-1 scatter reads its slice of digits ONCE
+//                  (16 per lane, kept in registers across count -> scan -> rank) and leaves coalesced runs per partition; then one workgroup
+//                  per partition orders its L2-resident entries and emits the bucket offsets — the staged kernel reads a partition that is
+//                  one chunk of at most 18 entries per lane ONCE as well                  (sort_scatter / sort_partition[_staged])
+//                  Bytes through HBM at 2^24 points x 13 windows: 32 B per scalar (0.5 GB) + five passes of 4 B per (point, window) —
+//                  dig written and read, tmp written and read, sorted written (0.87 GB each) = 4.9 GB, where the separate digits and
+//                  histogram kernels moved 5.7 GB and the second sweeps of both sort levels asked the caches for 1.7 GB more
+//                  (profiles/r07_msm_sort_passes.txt)
 //   3b. schedule   bucket ids counting-sorted by size, so a wave's lanes own equally loaded buckets
 //   4. accumulate  one lane per bucket walks its segment and adds the resident limb-form bases (negated for
 //                  negative digits) into an XYZZ accumulator held in VGPRs   (msm_accumulate_kernel;
@@ -82,49 +87,6 @@ __device__ __forceinline__ uint32_t scalar_raw_digit(const uint32_t* s, int bit0
     return (uint32_t)(v >> off) & ((1u << c) - 1);
 }
 
-// ---- 1: digits, planar: dig[w*n + i] = magnitude | sign << 31   (magnitude 0 = no contribution)
-// scalars_mont != 0: the scalars are Fr in Montgomery form and `into_repr` (commit_polynomial, worker.rs:117-123) is taken here,
-// on the fly, instead of in a separate pass that wrote 32 B per scalar to HBM and read them back.
-// `len` <= n scalars are valid; positions len .. n-1 get zero digits (a batch of commitments pads its shorter polynomials).
-__global__ void __launch_bounds__(256) msm_digits_kernel(const uint32_t* __restrict__ scalars, uint64_t n, uint64_t len, int c, int W,
-                                                         uint32_t* __restrict__ dig, int scalars_mont, const FpParams<8> FR) {
-    MSM_SIDE_PRIO_ENTER();
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (i >= len) {
-        for (int w = 0; w < W; w++) dig[(uint64_t)w * n + i] = 0;
-        return;
-    }
-    uint32_t s[8];
-    const uint4* sp = reinterpret_cast<const uint4*>(scalars + 8 * i);
-    const uint4 lo = sp[0], hi = sp[1];
-    s[0] = lo.x; s[1] = lo.y; s[2] = lo.z; s[3] = lo.w; s[4] = hi.x; s[5] = hi.y; s[6] = hi.z; s[7] = hi.w;
-    if (scalars_mont) {
-        Fp<8> v;
-#pragma unroll
-        for (int k = 0; k < 8; k++) v.l[k] = s[k];
-        v = fp_from_mont(v, FR);
-#pragma unroll
-        for (int k = 0; k < 8; k++) s[k] = v.l[k];
-    }
-    const uint32_t half = 1u << (c - 1);
-    uint32_t carry = 0;
-    for (int w = 0; w < W; w++) {
-        // static limb selection keeps s[] in registers
-        const int bit0 = w * c, limb = bit0 >> 5, off = bit0 & 31;
-        uint64_t v = 0;
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            if (k == limb) v |= s[k];
-            if (k == limb + 1) v |= (uint64_t)s[k] << 32;
-        }
-        uint32_t raw = ((uint32_t)(v >> off) & ((1u << c) - 1)) + carry;
-        carry = raw > half;
-        const uint32_t mag = carry ? (1u << c) - raw : raw;
-        dig[(uint64_t)w * n + i] = mag | (carry << 31);
-    }
-}
-
 // ---- 3: two-level LDS-staged counting sort of the (window, bucket) keys.
 // Level 1 splits every window into 2^lp partitions by the top bits of the bucket index (all traffic in
 // contiguous pieces, no global atomics: per-slice histograms + one exclusive scan give every (slice, partition)
@@ -148,24 +110,90 @@ struct SortGeom {
     uint32_t stage_cap;          // entries the staged level-2 kernel orders in LDS at a time (what its LDS budget leaves beside the counters and slice starts)
 };
 
-__global__ void __launch_bounds__(256) sort_hist_kernel(const uint32_t* __restrict__ dig, SortGeom g, uint32_t* __restrict__ blk_hist) {
+// ---- 1 + level-1 histograms in ONE pass over the scalars (one workgroup per (slice, scalar vector)).
+// Digits, planar: dig[w*n + i] = magnitude | sign << 31   (magnitude 0 = no contribution).
+// scalars_mont != 0: the scalars are Fr in Montgomery form and `into_repr` (commit_polynomial, worker.rs:117-123) is taken here,
+// on the fly, instead of in a separate pass that wrote 32 B per scalar to HBM and read them back.
+// `len` <= n scalars of a vector are valid; positions len .. n-1 get zero digits (a batch of commitments pads its shorter polynomials).
+// Every lane cuts its scalars into all W1 digits, writes them and counts each in the LDS histogram of its window: the digits are not
+// read back for the histograms (one launch per vector and one pass over `dig` less than a digits kernel followed by a histogram kernel).
+// The W1 * (2^lp + 1) counters of a vector are taken in GROUPS of `wgroup` windows where they outgrow DIGHIST_LDS_WORDS (narrow windows:
+// many of them); the groups after the first read back the digits this very lane wrote.
+#define MSM_MAX_GROUP 64                      // scalar vectors per launch set (msm_group)
+#define DIGHIST_THREADS 1024                  // 16 scalars per lane; two workgroups = eight waves per SIMD
+#define DIGHIST_LDS_WORDS (78 * 256)          // 78 KiB of counters at most: two workgroups per CU, like the level-1 scatter
+struct ScalarVecs {
+    const uint32_t* ptr[MSM_MAX_GROUP];
+    uint64_t len[MSM_MAX_GROUP];
+};
+__global__ void __launch_bounds__(DIGHIST_THREADS, 8) sort_digits_hist_kernel(const ScalarVecs sv, SortGeom g, int c, int W1, int wgroup, uint32_t* dig,
+                                                                           uint32_t* __restrict__ blk_hist, int scalars_mont, const FpParams<8> FR) {
     MSM_SIDE_PRIO_ENTER();
-    extern __shared__ uint32_t h[];
+    extern __shared__ uint32_t h[];                       // [wgroup][2^lp + 1], last bin of a window: zero digits
     const uint32_t np = (1u << g.lp) + 1;
-    for (uint32_t k = threadIdx.x; k < np; k += blockDim.x) h[k] = 0;
-    __syncthreads();
-    const uint32_t w = blockIdx.y, blk = blockIdx.x;
+    const uint32_t kv = blockIdx.y, blk = blockIdx.x;
+    const uint32_t* __restrict__ scalars = sv.ptr[kv];
+    const uint64_t len = sv.len[kv];
     const uint64_t beg = (uint64_t)blk * SORT_SLICE, end = beg + SORT_SLICE < g.n ? beg + SORT_SLICE : g.n;
-    const uint32_t* d = dig + (uint64_t)w * g.n;
-    for (uint64_t i = beg + threadIdx.x; i < end; i += blockDim.x) {
-        const uint32_t mag = d[i] & 0x7fffffffu;
-        const uint32_t part = mag ? ((mag - 1) >> g.low_bits) : (np - 1);
-        atomicAdd(&h[part], 1u);
-    }
-    __syncthreads();
-    for (uint32_t k = threadIdx.x; k < np; k += blockDim.x) {
-        const uint64_t pid = (k == np - 1) ? (uint64_t)g.nreal + w : ((uint64_t)w << g.lp) + k;
-        blk_hist[pid * g.nblk + blk] = h[k];
+    uint32_t* d = dig + (uint64_t)kv * W1 * g.n;
+    const uint32_t half = 1u << (c - 1);
+    for (int w0 = 0; w0 < W1; w0 += wgroup) {
+        const int w1 = w0 + wgroup < W1 ? w0 + wgroup : W1;
+        const uint32_t nh = (uint32_t)(w1 - w0) * np;
+        for (uint32_t k = threadIdx.x; k < nh; k += blockDim.x) h[k] = 0;
+        __syncthreads();
+        for (uint64_t i = beg + threadIdx.x; i < end; i += blockDim.x) {
+            if (w0 > 0) {                                 // later group: the digits are there
+                for (int w = w0; w < w1; w++) {
+                    const uint32_t mag = d[(uint64_t)w * g.n + i] & 0x7fffffffu;
+                    atomicAdd(&h[(uint32_t)(w - w0) * np + (mag ? ((mag - 1) >> g.low_bits) : (np - 1))], 1u);
+                }
+                continue;
+            }
+            if (i >= len) {
+                for (int w = 0; w < W1; w++) {
+                    d[(uint64_t)w * g.n + i] = 0;
+                    if (w < w1) atomicAdd(&h[(uint32_t)w * np + (np - 1)], 1u);
+                }
+                continue;
+            }
+            uint32_t s[8];
+            const uint4* sp = reinterpret_cast<const uint4*>(scalars + 8 * i);
+            const uint4 lo = sp[0], hi = sp[1];
+            s[0] = lo.x; s[1] = lo.y; s[2] = lo.z; s[3] = lo.w; s[4] = hi.x; s[5] = hi.y; s[6] = hi.z; s[7] = hi.w;
+            if (scalars_mont) {
+                Fp<8> v;
+#pragma unroll
+                for (int k = 0; k < 8; k++) v.l[k] = s[k];
+                v = fp_from_mont(v, FR);
+#pragma unroll
+                for (int k = 0; k < 8; k++) s[k] = v.l[k];
+            }
+            uint32_t carry = 0;
+            for (int w = 0; w < W1; w++) {
+                // static limb selection keeps s[] in registers
+                const int bit0 = w * c, limb = bit0 >> 5, off = bit0 & 31;
+                uint64_t v = 0;
+#pragma unroll
+                for (int k = 0; k < 8; k++) {
+                    if (k == limb) v |= s[k];
+                    if (k == limb + 1) v |= (uint64_t)s[k] << 32;
+                }
+                const uint32_t raw = ((uint32_t)(v >> off) & ((1u << c) - 1)) + carry;
+                carry = raw > half;
+                const uint32_t mag = carry ? (1u << c) - raw : raw;
+                d[(uint64_t)w * g.n + i] = mag | (carry << 31);
+                if (w < w1) atomicAdd(&h[(uint32_t)w * np + (mag ? ((mag - 1) >> g.low_bits) : (np - 1))], 1u);
+            }
+        }
+        __syncthreads();
+        for (uint32_t k = threadIdx.x; k < nh; k += blockDim.x) {
+            const uint32_t wl = k / np, kk = k - wl * np;
+            const uint64_t w = (uint64_t)kv * W1 + w0 + wl;           // window of the whole batch
+            const uint64_t pid = (kk == np - 1) ? (uint64_t)g.nreal + w : (w << g.lp) + kk;
+            blk_hist[pid * g.nblk + blk] = h[k];
+        }
+        __syncthreads();                                  // the counters are free for the next group
     }
 }
 
@@ -174,7 +202,8 @@ __global__ void __launch_bounds__(256) sort_hist_kernel(const uint32_t* __restri
 // partition in LDS (counts -> exclusive scan -> ranks), then copied out with consecutive lanes writing consecutive
 // addresses of each partition's run.
 #define SCATTER_THREADS 1024     // 16 waves on a ~74 KiB LDS footprint: two workgroups = eight waves per SIMD hide the LDS-atomic and HBM latency
-__global__ void __launch_bounds__(SCATTER_THREADS) sort_scatter_kernel(const uint32_t* __restrict__ dig, SortGeom g, const uint32_t* __restrict__ blk_off,
+#define SCATTER_PER (SORT_SLICE / SCATTER_THREADS)      // digits of the slice per lane
+__global__ void __launch_bounds__(SCATTER_THREADS, 8) sort_scatter_kernel(const uint32_t* __restrict__ dig, SortGeom g, const uint32_t* __restrict__ blk_off,
                                                                        uint32_t* __restrict__ tmp) {
     MSM_SIDE_PRIO_ENTER();
     extern __shared__ uint32_t sm[];
@@ -187,9 +216,18 @@ __global__ void __launch_bounds__(SCATTER_THREADS) sort_scatter_kernel(const uin
     __syncthreads();
     const uint64_t beg = (uint64_t)blk * SORT_SLICE, end = beg + SORT_SLICE < g.n ? beg + SORT_SLICE : g.n;
     const uint32_t* d = dig + (uint64_t)w * g.n;
-    for (uint64_t i = beg + threadIdx.x; i < end; i += blockDim.x) {
-        const uint32_t mag = d[i] & 0x7fffffffu;
-        atomicAdd(&cnt[mag ? ((mag - 1) >> g.low_bits) : (np - 1)], 1u);
+    // the lane's SCATTER_PER digits are read ONCE and stay in registers for the rank sweep below; what lies beyond `end` (the last, partial
+    // slice) reads as a zero digit, which neither sweep counts (the zero bin stays empty here: only the histogram kernel needs it)
+    uint32_t e[SCATTER_PER];
+#pragma unroll
+    for (int r = 0; r < SCATTER_PER; r++) {
+        const uint64_t i = beg + threadIdx.x + (uint32_t)r * SCATTER_THREADS;
+        e[r] = i < end ? d[i] : 0u;
+    }
+#pragma unroll
+    for (int r = 0; r < SCATTER_PER; r++) {
+        const uint32_t mag = e[r] & 0x7fffffffu;
+        if (mag) atomicAdd(&cnt[(mag - 1) >> g.low_bits], 1u);
     }
     __syncthreads();
     // exclusive scan of the np counts (np <= 8193): every lane a contiguous strip, then a strip-sum scan
@@ -215,12 +253,13 @@ __global__ void __launch_bounds__(SCATTER_THREADS) sort_scatter_kernel(const uin
     const uint32_t low_mask = (1u << g.low_bits) - 1;
     const uint32_t ebits = (uint32_t)g.low_bits + SORT_SLICE_LOG + 1;
     const bool packed = ebits + (uint32_t)g.lp <= 32;
-    for (uint64_t i = beg + threadIdx.x; i < end; i += blockDim.x) {
-        const uint32_t e = d[i], mag = e & 0x7fffffffu;
+#pragma unroll
+    for (int r = 0; r < SCATTER_PER; r++) {
+        const uint32_t mag = e[r] & 0x7fffffffu;
         if (!mag) continue;
         const uint32_t key = mag - 1, part = key >> g.low_bits;
         const uint32_t pos = atomicAdd(&cnt[part], 1u);
-        uint32_t v = ((key & low_mask) << (SORT_SLICE_LOG + 1)) | ((e >> 31) << SORT_SLICE_LOG) | (uint32_t)(i - beg);
+        uint32_t v = ((key & low_mask) << (SORT_SLICE_LOG + 1)) | ((e[r] >> 31) << SORT_SLICE_LOG) | (threadIdx.x + (uint32_t)r * SCATTER_THREADS);
         if (packed && g.lp) v |= part << ebits;
         buf[pos] = v;
     }
@@ -328,7 +367,8 @@ __global__ void __launch_bounds__(256) sort_partition_kernel(const uint32_t* __r
 // such partitions — all of them at 2^25 and 2^26 points — fell back to the direct kernel: sort 17.3 / 35.6 ms beside 30.6 / 59.9 ms of accumulation.
 #define STAGE_THREADS 1024
 #define STAGE_MAX_CHUNKS 8u
-__global__ void __launch_bounds__(STAGE_THREADS) sort_partition_staged_kernel(const uint32_t* __restrict__ tmp, SortGeom g, const uint32_t* __restrict__ blk_off,
+#define STAGE_KEEP 18              // entries a lane keeps in registers between the two sweeps: 18 * 1024 = the largest buffer the 78 KiB leave at 2^24 points
+__global__ void __launch_bounds__(STAGE_THREADS, 8) sort_partition_staged_kernel(const uint32_t* __restrict__ tmp, SortGeom g, const uint32_t* __restrict__ blk_off,
                                                                               uint32_t* __restrict__ sorted, uint32_t* __restrict__ offsets, const SizeHist sz) {
     MSM_SIDE_PRIO_ENTER();
     extern __shared__ uint32_t lds[];
@@ -347,7 +387,21 @@ __global__ void __launch_bounds__(STAGE_THREADS) sort_partition_staged_kernel(co
     if (!g.idx_bits)
         for (uint32_t k = threadIdx.x; k < g.nblk; k += blockDim.x) run0[k] = po[k];
     __syncthreads();
-    for (uint32_t j = pbeg + threadIdx.x; j < pend; j += blockDim.x) atomicAdd(&cnt[tmp[j] >> sh], 1u);
+    // The common case — the partition fits the buffer in one chunk AND a lane's share fits STAGE_KEEP registers — reads the partition ONCE: the
+    // entries of the count sweep stay in registers for the placement.  Everything else (chunks, the direct path, a partition of more than
+    // STAGE_KEEP * STAGE_THREADS entries) streams it again below.
+    const bool keep = len <= g.stage_cap && len <= (uint32_t)STAGE_KEEP * STAGE_THREADS;
+    uint32_t ent[STAGE_KEEP];
+    if (keep) {
+#pragma unroll
+        for (int r = 0; r < STAGE_KEEP; r++) {
+            const uint32_t j = pbeg + threadIdx.x + (uint32_t)r * STAGE_THREADS;
+            ent[r] = j < pend ? tmp[j] : 0u;
+            if (j < pend) atomicAdd(&cnt[ent[r] >> sh], 1u);
+        }
+    } else {
+        for (uint32_t j = pbeg + threadIdx.x; j < pend; j += blockDim.x) atomicAdd(&cnt[tmp[j] >> sh], 1u);
+    }
     __syncthreads();
     // exclusive scan of the nlow (<= 2048) counts: two entries per lane at most, then a strip-sum scan
     const uint32_t per = (nlow + blockDim.x - 1) / blockDim.x;
@@ -376,6 +430,26 @@ __global__ void __launch_bounds__(STAGE_THREADS) sort_partition_staged_kernel(co
     if (sz.ghist && threadIdx.x < SIZE_BINS && shist[threadIdx.x]) atomicAdd(&sz.ghist[threadIdx.x], shist[threadIdx.x]);
     const uint32_t in_mask = SORT_SLICE - 1;
     const uint32_t imask = g.idx_bits ? (1u << g.idx_bits) - 1 : 0;
+    if (keep) {                                // one chunk from the registers: the cursors start at 0 and end at len
+#pragma unroll
+        for (int r = 0; r < STAGE_KEEP; r++) {
+            const uint32_t j = pbeg + threadIdx.x + (uint32_t)r * STAGE_THREADS;
+            if (j >= pend) continue;
+            const uint32_t e = ent[r];
+            uint32_t val;
+            if (g.idx_bits) {
+                val = (e & imask) | (((e >> g.idx_bits) & 1u) << 31);
+            } else {
+                uint32_t lo = 0, hi = g.nblk;  // slice = largest b with run0[b] <= j
+                while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (run0[mid] <= j) lo = mid; else hi = mid; }
+                val = ((lo << SORT_SLICE_LOG) + (e & in_mask)) | (((e >> SORT_SLICE_LOG) & 1u) << 31);
+            }
+            buf[atomicAdd(&cnt[e >> sh], 1u)] = val;
+        }
+        __syncthreads();
+        for (uint32_t j = threadIdx.x; j < len; j += blockDim.x) sorted[pbeg + j] = buf[j];
+        return;
+    }
     // chunks of consecutive buckets: one when the partition fits the buffer, else sized for 3/4 of it (bucket sizes fluctuate)
     const uint32_t cap = g.stage_cap;
     // (a partition far beyond that — the 2^14-bucket top window of a c = 20 decomposition puts 2^19 entries in each of its partitions — would stream
@@ -1476,16 +1550,22 @@ static int msm_slice(int curve, const BaseRec<NQ>* d_bases, const uint32_t* cons
     BucketL* grid_c = grid_r + ((size_t)Wr << g_logL);
     XyzzPt<NQ>* gbits = (XyzzPt<NQ>*)(base + o_gbits);
 
-    const size_t lds1 = ((size_t)(1u << g.lp) + 1) * 4;
-    { ProfScope ps("msm_digits_kernel", stream);
-    for (int k = 0; k < K; k++)
-        hipLaunchKernelGGL(msm_digits_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, d_scalars[k], (uint64_t)n, (uint64_t)lens[k], c, W1,
-                           dig + (size_t)k * W1 * n, scalars_mont ? 1 : 0, fr_params(curve)); }
     const bool fused_order = p.fused_order;
     const SizeHist szh{fused_order ? ghist : nullptr, sg.bin_shift, (uint64_t)nbuckets};
     if (fused_order) HIP_TRY(hipMemsetAsync(ghist, 0, 2 * SIZE_BINS * 4, stream));
     { ProfScope ps("msm_sort", stream);
-    hipLaunchKernelGGL(sort_hist_kernel, dim3(g.nblk, W), dim3(256), lds1, stream, dig, g, blk_hist);
+    {
+        // digits + level-1 histograms, one workgroup per (slice, vector); the windows of a vector in groups of what the LDS budget holds
+        if (K > MSM_MAX_GROUP) return plonk_fail(PLONK_ERR_ARG, "msm: %d vectors in one launch set", K);
+        ScalarVecs sv;
+        for (int k = 0; k < MSM_MAX_GROUP; k++) { sv.ptr[k] = k < K ? d_scalars[k] : nullptr; sv.len[k] = k < K ? (uint64_t)lens[k] : 0; }
+        const uint32_t np = (1u << g.lp) + 1;
+        const int wgroup = std::min<int>(W1, std::max<int>(1, (int)(DIGHIST_LDS_WORDS / np)));
+        static DeviceOnce attr0;
+        HIP_TRY(attr0.run([] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&sort_digits_hist_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); }));
+        hipLaunchKernelGGL(sort_digits_hist_kernel, dim3(g.nblk, (uint32_t)K), dim3(DIGHIST_THREADS), (size_t)wgroup * np * 4, stream, sv, g, c, W1, wgroup, dig,
+                           blk_hist, scalars_mont ? 1 : 0, fr_params(curve));
+    }
     hipLaunchKernelGGL(scan_block_sums_kernel, dim3((uint32_t)nscan_blocks), dim3(SCAN_THREADS), 0, stream, blk_hist, nhist, bsums);
     hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(1024), 0, stream, bsums, nscan_blocks, blk_off + nhist);
     hipLaunchKernelGGL(scan_apply_kernel, dim3((uint32_t)nscan_blocks), dim3(SCAN_THREADS), 0, stream, blk_hist, nhist, bsums, blk_off);

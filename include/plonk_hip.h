@@ -517,7 +517,7 @@ int plonk_last_kernel_ms(plonk_ctx* ctx, double* out_ms);
 
 /* Per-kernel timing with HIP events recorded on the context's stream around every kernel launch
  * (off by default).  Names: "ntt_pass_kernel", "ntt_pass_kernel<9>" (per in-LDS size),
- * "msm_digits_kernel", "msm_sort", "msm_bucket_order", "msm_accumulate_kernel", "msm_accumulate_redo_kernel", "msm_heavy",
+ * "msm_sort" (digits, histograms, scan, both sort levels), "msm_bucket_order", "msm_accumulate_kernel", "msm_accumulate_redo_kernel", "msm_heavy",
  * "msm_reduce", "quotient_evals_kernel", "perm_terms_kernel", "perm_scan_num", "perm_scan_den_final",
  * "poly_eval_kernel", "poly_lincomb_kernel", "poly_scale_kernel", "poly_div_scan", "rccl_alltoall", "rccl_allgather" (the collective
  * as the stream saw it, waiting for peers included).  total_ms / launches accumulate until reset. */
