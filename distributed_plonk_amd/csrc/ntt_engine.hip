@@ -172,9 +172,12 @@ static int get_plane(NttTables& T, int log_m, int log_rprev, int log_rp, int dir
     }
     Fr* d = nullptr;
     if (hipMalloc((void**)&d, bytes) != hipSuccess) { (void)hipGetLastError(); plane_fallback_notice("hipMalloc failed", bytes); return PLONK_OK; }
-    hipLaunchKernelGGL(ntt_gen_plane_kernel, dim3((uint32_t)((r_prev + 255) / 256)), dim3(256), 0, stream, d, r_prev, (uint64_t)1 << log_rp, lo,
-                       T.tw_hi[dir], (uint32_t)T.lt, (uint32_t)(T.two_adicity - log_rprev), fold_coset ? T.g_lo[0] : (const F29*)nullptr,
-                       fold_coset ? T.g_hi[0] : (const F29*)nullptr, (uint64_t)1 << log_coset_mult, T.fp29);
+    {
+        ProfScope ps("ntt_gen_plane", stream);
+        hipLaunchKernelGGL(ntt_gen_plane_kernel, dim3((uint32_t)((r_prev + 255) / 256)), dim3(256), 0, stream, d, r_prev, (uint64_t)1 << log_rp, lo,
+                           T.tw_hi[dir], (uint32_t)T.lt, (uint32_t)(T.two_adicity - log_rprev), fold_coset ? T.g_lo[0] : (const F29*)nullptr,
+                           fold_coset ? T.g_hi[0] : (const F29*)nullptr, (uint64_t)1 << log_coset_mult, T.fp29);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { (void)hipFree(d); return plonk_fail(PLONK_ERR_HIP, "ntt_gen_plane launch: %s", hipGetErrorString(e)); }
     T.planes[key] = d;
@@ -195,9 +198,12 @@ static int get_epi_plane(NttTables& T, int log_N, int log_M, uint64_t batch, uin
     if (T.plane_bytes + bytes > T.plane_budget) return PLONK_OK;
     Fr* d = nullptr;
     if (hipMalloc((void**)&d, bytes) != hipSuccess) { (void)hipGetLastError(); return PLONK_OK; }
-    hipLaunchKernelGGL(ntt_gen_epi_plane_kernel, dim3((uint32_t)((M * batch + 255) / 256)), dim3(256), 0, stream, d, M, batch, q0, T.tw_lo[dir],
-                       T.tw_hi[dir], (uint32_t)T.lt, (uint32_t)(T.two_adicity - log_N), fold_coset ? T.g_lo[0] : (const F29*)nullptr,
-                       fold_coset ? T.g_hi[0] : (const F29*)nullptr, T.fp29);
+    {
+        ProfScope ps("ntt_gen_epi_plane", stream);
+        hipLaunchKernelGGL(ntt_gen_epi_plane_kernel, dim3((uint32_t)((M * batch + 255) / 256)), dim3(256), 0, stream, d, M, batch, q0, T.tw_lo[dir],
+                           T.tw_hi[dir], (uint32_t)T.lt, (uint32_t)(T.two_adicity - log_N), fold_coset ? T.g_lo[0] : (const F29*)nullptr,
+                           fold_coset ? T.g_hi[0] : (const F29*)nullptr, T.fp29);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { (void)hipFree(d); return plonk_fail(PLONK_ERR_HIP, "ntt_gen_epi_plane launch: %s", hipGetErrorString(e)); }
     T.planes[key] = d;
@@ -299,6 +305,7 @@ static int get_shift_set(NttTables& T, const Fr& h, int L, uint64_t B, int w0, i
         HIP_TRY(hipMemcpyAsync(d_pw, h_pw.data(), h_pw.size() * sizeof(F29), hipMemcpyHostToDevice, stream));
         for (uint64_t q = 0; q < B; q++) {
             const F29* lo = d_pw + q * (1024 + n_hi);
+            ProfScope ps("ntt_gen_shift_plane", stream);
             hipLaunchKernelGGL(ntt_gen_shift_plane_kernel, dim3((uint32_t)((M + 255) / 256)), dim3(256), 0, stream, set.planes + q * M, M, r1, T.tw_lo[0],
                                T.tw_hi[0], (uint32_t)T.lt, (uint32_t)(T.two_adicity - L), lo, lo + 1024, T.fp29);
         }

@@ -262,6 +262,10 @@ extern "C" int plonk_set_option(plonk_ctx* ctx, const char* key, int64_t value) 
         ctx->tables.use_shoup = value != 0;
         return PLONK_OK;
     }
+    if (!strcmp(key, "ntt_plane_budget")) {       // tests: BYTES of factor planes this context may hold (< 0: the default); applies from the next transform, frees nothing
+        ctx->tables.plane_budget = value < 0 ? NTT_PLANE_BUDGET_DEFAULT : (size_t)value;
+        return PLONK_OK;
+    }
     if (!strcmp(key, "quotient_fuse")) { ctx->tables.quotient_fuse = (int)value; return PLONK_OK; }   // experiments, see quotient.hip
     if (!strcmp(key, "msm_slice_log")) { ctx->msm_ws.slice_log = (int)value; return PLONK_OK; }       // MSMs above 2^value points are sliced (8..26)
     return plonk_fail(PLONK_ERR_ARG, "plonk_set_option: unknown key %s", key);

@@ -73,6 +73,7 @@ struct ProfScope {       // RAII: brackets the launches issued in its lifetime
 };
 
 // ----------------------------------------------------------------------------------------------- NTT
+constexpr size_t NTT_PLANE_BUDGET_DEFAULT = (size_t)48 << 30;
 struct NttTables {
     int curve = 0;
     FrParams fp;
@@ -99,7 +100,7 @@ struct NttTables {
     };
     std::unordered_map<std::string, ShiftSet> shift_sets;
     size_t plane_bytes = 0;                       // HBM currently held by planes
-    size_t plane_budget = (size_t)48 << 30;       // stop creating planes beyond this (fall back to on-the-fly factors)
+    size_t plane_budget = NTT_PLANE_BUDGET_DEFAULT;   // stop creating planes beyond this (fall back to on-the-fly factors); option "ntt_plane_budget"
     // quotient.hip: g * w_Nmax^e (constant form) and 1/(x_i - 1) per quotient-domain size (key = log m)
     F29* quot_x_lo = nullptr;
     std::unordered_map<int, Fr*> quot_inv_xm1;     // key: log m | class stride << 8 | class offset << 16

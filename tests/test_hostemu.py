@@ -114,6 +114,16 @@ def test_distributed_transform_steps_and_coset_classes(emu_env):
     _run_gpu_tests(emu_env, ["tests/test_gpu_coset_classes.py"], k="not full_size and not 1048579")
 
 
+def test_ntt_plane_budget_routes(emu_env):
+    """tests/test_gpu_ntt_plane_budget.py: the pass kernel's plane-less branches (inter-pass factors, output factors and the coset prologue formed
+    on the fly), the plain plane beside a prologue shift, mixed plans, the distributed passes under budget 0, shift-set refusal / eviction and
+    the accounting behind plonk_trim — the BN254 cases at the smallest size of each group, each asserting its route from the plane generators'
+    launch counts (the emulated runtime has events, so the profiling scopes count as on the device)."""
+    out = _run_gpu_tests(emu_env, ["tests/test_gpu_ntt_plane_budget.py"],
+                         k="bn254 and (n9r3 or n10r9 or n7r3 or 2-9-bn254 or 2-3-bn254 or 6-100 or 9-70 or compact) or per_step")
+    assert "19 passed" in out, out
+
+
 def test_batched_commitments_and_fixed_base_table(emu_env):
     _run_gpu_tests(emu_env, ["tests/test_gpu_commit_many.py"], k="not full_size and not group_limit")
     _run_gpu_tests(emu_env, ["tests/test_gpu_msm_table.py"], k="bn254")

@@ -44,6 +44,7 @@ class Fuzz:
         self.w = PlonkWorker(me=0, device=0, curve=curve)
         self.f = _fr.FIELDS[curve]
         self.rs = np.random.RandomState(seed)
+        self.rs_budget = np.random.RandomState((seed ^ 0x9E3779B9) & 0x7FFFFFFF)    # op_ntt's plane budgets: a stream of its own, so that a seed draws the operations and shapes it always drew
         self.max_log = max_log
         self.counter = 0
         self.n_bases = 0
@@ -90,11 +91,18 @@ class Fuzz:
         n = 1 << log_n
         inv, coset = bool(self.rs.randint(0, 2)), bool(self.rs.randint(0, 2))
         v = self.fr(n)
+        # plonk_ntt_dev cannot fail for lack of factor planes: no plane at all (factors formed on the fly), room for the first pass's alone (whatever
+        # earlier operations left cached counts against it), or the default
+        budget = (0, n * 32, -1)[int(self.rs_budget.randint(0, 3))]
         d_in, d_out = self.up(v), self.w.alloc(n * 32)
-        self.w.ntt_dev(d_in.ptr, d_out.ptr, n, inv, coset)
-        got = d_out.download((n, 4))
-        d_in.free(); d_out.free()
-        return np.array_equal(got, self.O.ntt(self.cid, v, inv, coset, threads=4)), dict(log_n=log_n, inv=inv, coset=coset)
+        try:
+            self.w.set_option("ntt_plane_budget", budget)
+            self.w.ntt_dev(d_in.ptr, d_out.ptr, n, inv, coset)
+            got = d_out.download((n, 4))
+        finally:
+            self.w.set_option("ntt_plane_budget", -1)
+            d_in.free(); d_out.free()
+        return np.array_equal(got, self.O.ntt(self.cid, v, inv, coset, threads=4)), dict(log_n=log_n, inv=inv, coset=coset, plane_budget=budget)
 
     def op_coset_eval_interp(self):
         log_s = int(self.rs.randint(1, self.max_log + 1))
