@@ -174,11 +174,11 @@ struct MsmWorkspace {
     int fused_y3 = 1;         // "msm_fused_y3": Y3 of the mixed addition under one Montgomery reduction (ec_lazy.hpp); 0 = two products
     int sort_stage_cap = 0;   // "msm_sort_stage_cap": > 0 caps the LDS staging buffer of the level-2 sort (entries; tests force its chunked path), 0 = what the LDS budget leaves
     int sort_slice_index = 0; // "msm_sort_slice_index": 1 = level-1 sort entries carry the index within their 2^14-point slice at any size (idx_bits = 0; tests: the form that windows >= 19 bits take above 2^22 points)
-    int reduce_grid = 0;      // "msm_reduce_grid": 1 = the window reduction as row / column tree sums + bit sums (msm_grid_sums_kernel) instead of the running-sum pyramid; experiment, not measured yet
+    int reduce_grid = 0;      // "msm_reduce_grid": 1 = the window reduction as row / column tree sums + bit sums (msm_grid_sums_kernel) instead of the running-sum pyramid; measured and lost to the pyramid (profiles/r06_small_msm_ab.txt), kept as an option
     int acc_persist = 4;      // "msm_acc_persist": workgroups per CU of the persistent bucket accumulation (0 = one lane per bucket over the whole grid; < 0: an absolute grid of that many workgroups, for tests)
 };
 void msm_ws_release(MsmWorkspace& ws);
-// Fixed-base window table (msm_engine.hip: msm_table_kernel): T planes of `stride` points, plane t = 2^(c*G*t) * bases; a scalar vector's W windows
+// Fixed-base window table (msm_kernels.hpp: msm_table_kernel): T planes of `stride` points, plane t = 2^(c*G*t) * bases; a scalar vector's W windows
 // accumulate into G bucket sets (window g + t*G reads plane t).
 struct MsmTable {
     int c = 0;            // 0 = no table (plane 0 only)
@@ -188,7 +188,7 @@ struct MsmTable {
     uint64_t stride = 0;  // points per plane (= n_bases)
     bool force = false;   // msm_precompute = 2: use the table for every MSM it can serve, whatever the cost model says (tests, experiments)
 };
-// bases: device, RESIDENT FORM produced by bases_to_limbs() (64 B BN254 / 96 B BLS12-381 per point: msm_engine.hip, BaseRec); with a table,
+// bases: device, RESIDENT FORM produced by bases_to_limbs() (64 B BN254 / 96 B BLS12-381 per point: msm_kernels.hpp, BaseRec); with a table,
 // the pointer addresses plane 0 (+ the range start) and the other planes follow at multiples of tab.stride.
 // scalars: device, canonical 8xu32 — or Montgomery-form Fr when scalars_mont (into_repr is then taken inside the digit kernel).
 // out_jac: host, 3*Q*... written as X||Y||Z Montgomery u32 limbs.

@@ -1,5 +1,6 @@
 """The MSM engine's host planner and its digit decomposition restated for the tests that force plan shapes (tests/test_gpu_msm_plans.py):
-`plan` is msm_plan / plan_window / sort_geometry / msm_group of csrc/msm_engine.hip written again in Python and compared field by field with
+`plan` is msm_plan / plan_window / sort_geometry / msm_group / msm_launch_sets of csrc/msm_engine.hip (the host side; the kernels are
+csrc/msm_kernels.hpp) written again in Python and compared field by field with
 what the engine reports through plonk_msm_plan; `signed_digits`, `partition_lengths`, `chunks`, `chunk_entries` and `heavy_buckets` restate the
 data-dependent choices of msm_digits_kernel, sort_partition_staged_kernel and msm_accumulate_kernel, so that a case can say before it runs which
 of their branches its scalars reach; PLAN_CASES is the case table, every row naming the branches it exists for (FEATURES)."""

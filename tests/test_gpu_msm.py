@@ -284,7 +284,7 @@ def test_bucket_ordering_fused_into_the_sort_matches_the_three_launch_form(gpu_w
 @pytest.mark.parametrize("curve,cid", [("bn254", 0), ("bls12_381", 1)])
 def test_grid_reduction_matches_pyramid_and_oracle(gpu_workers, oracle, curve, cid):
     """`msm_reduce_grid` (experiment, off by default): the window reduction V = sum_j (j+1) B_j as row / column tree sums of the H x L bucket
-    grid plus bit sums of the <= 1024 row / column totals (msm_engine.hip, 5b) instead of the running-sum pyramid.  Every window width from
+    grid plus bit sums of the <= 1024 row / column totals (msm_kernels.hpp, 5b) instead of the running-sum pyramid.  Every window width from
     3 bits (a 2 x 2 grid) to 13 (64 x 64) and the plan's own choice — odd and even bucket-index widths, grids narrower than a workgroup's
     column / row coverage — with duplicated bases (P + P inside the trees), an infinity base, all scalars equal (one non-empty bucket per window:
     every other tree input is the point at infinity), scalars 0 / 1 / p - 1, and a batched round; against the pyramid and the oracle."""

@@ -17,8 +17,8 @@ CURVES = [("bn254", 0), ("bls12_381", 1)]
 RESTORE = {"msm_window": 0, "msm_fused_order": 1, "msm_sort_stage_cap": 0, "msm_sort_slice_index": 0, "msm_reduce_grid": 0, "msm_fused_y3": 1,
            "msm_acc_persist": 4}
 SLICE = 1 << M.SORT_SLICE_LOG
-STAGE_KEEP = 18                      # entries per lane the staged level-2 kernel keeps in registers (csrc/msm_engine.hip)
-DIGHIST_LDS_WORDS = 78 * 256         # histogram counters of the level-1 kernel per window group (csrc/msm_engine.hip)
+STAGE_KEEP = 18                      # entries per lane the staged level-2 kernel keeps in registers (csrc/msm_kernels.hpp)
+DIGHIST_LDS_WORDS = 78 * 256         # histogram counters of the level-1 kernel per window group (csrc/msm_kernels.hpp)
 _cache = {}
 
 
