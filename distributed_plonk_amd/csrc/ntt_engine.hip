@@ -88,6 +88,11 @@ int ntt_tables_create(NttTables& T, int curve, hipStream_t stream) {
     return PLONK_OK;
 }
 
+static void shift_set_free(NttTables::ShiftSet& s) {
+    (void)hipFree(s.planes); (void)hipFree(s.rowtabs); (void)hipFree(s.foldc); (void)hipFree(s.ctw);
+    s.planes = nullptr; s.rowtabs = nullptr; s.foldc = nullptr; s.ctw = nullptr;
+}
+
 // Everything a context can rebuild on demand: inter-pass / output-factor planes, coset row tables, the first-pass tables of class-decomposed
 // evaluations, the quotient kernel's 1/(x - 1) planes, power tables — not the root tables the domains were set up with.  -> bytes' worth of
 // entries released (the planes' share is T.plane_bytes; the rest is small).
@@ -98,7 +103,9 @@ void ntt_tables_trim(NttTables& T) {
     T.planes.clear();
     for (auto& kv : T.rowtabs) (void)hipFree(kv.second);
     T.rowtabs.clear();
-    for (auto& kv : T.shift_sets) { (void)hipFree(kv.second.planes); (void)hipFree(kv.second.rowtabs); (void)hipFree(kv.second.foldc); }
+    for (auto& kv : T.ctw_tabs) (void)hipFree(kv.second);
+    T.ctw_tabs.clear();
+    for (auto& kv : T.shift_sets) shift_set_free(kv.second);
     T.shift_sets.clear();
     T.plane_bytes = 0;
     for (auto& kv : T.quot_inv_xm1) (void)hipFree(kv.second);
@@ -120,7 +127,9 @@ void ntt_tables_destroy(NttTables& T) {
     T.planes.clear();
     for (auto& kv : T.rowtabs) (void)hipFree(kv.second);
     T.rowtabs.clear();
-    for (auto& kv : T.shift_sets) { (void)hipFree(kv.second.planes); (void)hipFree(kv.second.rowtabs); (void)hipFree(kv.second.foldc); }
+    for (auto& kv : T.ctw_tabs) (void)hipFree(kv.second);
+    T.ctw_tabs.clear();
+    for (auto& kv : T.shift_sets) shift_set_free(kv.second);
     T.shift_sets.clear();
     T.plane_bytes = 0;
     if (T.quot_x_lo) { (void)hipFree(T.quot_x_lo); T.quot_x_lo = nullptr; }
@@ -228,6 +237,33 @@ static int get_rowtab(NttTables& T, int log_r1, int log_w, F29** out, hipStream_
     return PLONK_OK;
 }
 
+// Coset twiddles of a first pass of width w whose row scale is s^a (ntt_kernels.hpp: the folded first pass), appended to `h`: for every stage
+// sigma < w the 2^sigma prepared constants s^(R / 2^(sigma+1)) * w_(2^(sigma+1))^j — R - 1 entries, forward direction.
+static void host_coset_twiddles(std::vector<F29S>& h, const Fr& s, int w, const NttTables& T) {
+    for (int sg = 0; sg < w; sg++) {
+        const Fr root = host_pow2k(T.h_root[0], T.two_adicity - (sg + 1), T.fp);
+        Fr acc = host_pow2k(s, w - sg - 1, T.fp);
+        for (uint32_t j = 0; j < (1u << sg); j++) { h.push_back(f29_shoup_from_mont256(acc, T.fp)); acc = fp_mul(acc, root, T.fp); }
+    }
+}
+
+// the coset twiddles beside get_rowtab's table: s = g^(2^log_r1), one table per (log_r1, width)
+static int get_coset_tw(NttTables& T, int log_r1, int log_w, const F29S** out, hipStream_t stream) {
+    const uint64_t key = ((uint64_t)log_r1 << 8) | (uint64_t)log_w;
+    auto it = T.ctw_tabs.find(key);
+    if (it != T.ctw_tabs.end()) { *out = it->second; return PLONK_OK; }
+    const uint32_t* g_l = T.curve == PLONK_BN254 ? BN254_FR_GENERATOR_MONT : BLS12_381_FR_GENERATOR_MONT;
+    std::vector<F29S> h;
+    host_coset_twiddles(h, host_pow2k(fp_from_limbs<8>(g_l), log_r1, T.fp), log_w, T);
+    F29S* d = nullptr;
+    HIP_TRY(hipMalloc((void**)&d, h.size() * sizeof(F29S)));
+    T.ctw_tabs[key] = d;
+    HIP_TRY(hipMemcpyAsync(d, h.data(), h.size() * sizeof(F29S), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    *out = d;
+    return PLONK_OK;
+}
+
 // c * base^i, i < count, appended to `h` in constant form
 static void host_powers_const(std::vector<F29>& h, const Fr& base, size_t count, const FrParams& P) {
     Fr r261;
@@ -242,7 +278,8 @@ static void host_powers_const(std::vector<F29>& h, const Fr& base, size_t count,
 }
 
 // First-pass tables for the evaluation of one coefficient vector on the B cosets h_q * <w_M>, h_q = h * w_(M*B)^q:
-// row tables h_q^(a*r_1), fold constants (h_q^M)^u and — for transforms of more than one pass — the planes w_M^(b*i) * h_q^b.
+// row tables h_q^(a*r_1), fold constants (h_q^M)^u and — for transforms of more than one pass — the planes w_M^(b*i) * h_q^b and, where the
+// first pass has the folded form (width >= 5), the coset twiddles of s_q = h_q^r_1 (small like the row tables: not counted in `bytes`).
 // Cached per (h, log M, log B, first pass width); planes count against the plane budget (older sets are dropped to make room;
 // running out of memory is an ERROR here, not a silent slow path: there is no plane-less variant of this transform).
 static int get_shift_set(NttTables& T, const Fr& h, int L, uint64_t B, int w0, int NP, const NttTables::ShiftSet** out, hipStream_t stream) {
@@ -259,8 +296,8 @@ static int get_shift_set(NttTables& T, const Fr& h, int L, uint64_t B, int w0, i
     if (T.plane_bytes + set.bytes > T.plane_budget && !T.shift_sets.empty()) {        // make room: drop the other shift sets
         HIP_TRY(hipStreamSynchronize(stream));
         for (auto& kv : T.shift_sets) {
-            (void)hipFree(kv.second.planes); (void)hipFree(kv.second.rowtabs); (void)hipFree(kv.second.foldc);
             T.plane_bytes -= kv.second.bytes;
+            shift_set_free(kv.second);
         }
         T.shift_sets.clear();
     }
@@ -279,12 +316,19 @@ static int get_shift_set(NttTables& T, const Fr& h, int L, uint64_t B, int w0, i
     }
     struct Guard {                 // frees whatever has been allocated unless the set is handed over
         NttTables::ShiftSet* s; F29* extra = nullptr; bool armed = true;
-        ~Guard() { if (armed) { (void)hipFree(s->planes); (void)hipFree(s->rowtabs); (void)hipFree(s->foldc); } (void)hipFree(extra); }
+        ~Guard() { if (armed) shift_set_free(*s); (void)hipFree(extra); }
     } guard{&set};
     HIP_TRY(hipMalloc((void**)&set.rowtabs, h_row.size() * sizeof(F29)));
     HIP_TRY(hipMalloc((void**)&set.foldc, h_fold.size() * sizeof(F29)));
     HIP_TRY(hipMemcpyAsync(set.rowtabs, h_row.data(), h_row.size() * sizeof(F29), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemcpyAsync(set.foldc, h_fold.data(), h_fold.size() * sizeof(F29), hipMemcpyHostToDevice, stream));
+    std::vector<F29S> h_ctw;
+    if (NP > 1 && w0 >= 5) {
+        h_ctw.reserve(B * (R1 - 1));
+        for (uint64_t q = 0; q < B; q++) host_coset_twiddles(h_ctw, host_pow2k(hq[q], L - w0, P), w0, T);
+        HIP_TRY(hipMalloc((void**)&set.ctw, h_ctw.size() * sizeof(F29S)));
+        HIP_TRY(hipMemcpyAsync(set.ctw, h_ctw.data(), h_ctw.size() * sizeof(F29S), hipMemcpyHostToDevice, stream));
+    }
     HIP_TRY(hipStreamSynchronize(stream));
     if (NP > 1) {
         if (hipMalloc((void**)&set.planes, set.bytes) != hipSuccess) {
@@ -387,18 +431,22 @@ static int ntt_ept() {
     return ept;
 }
 
-template <int LOG_R, int EPT, bool SWZ = false, bool SHOUP = false>
+template <int LOG_R, int EPT, bool SWZ = false, bool SHOUP = false, bool CTW = false>
 static hipError_t launch_one_e(const NttPassParams& P, uint64_t grid, uint32_t threads, size_t lds, hipStream_t stream) {
     static DeviceOnce attr;
-    hipError_t e = attr.run([] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&ntt_pass_kernel<LOG_R, EPT, SWZ, SHOUP>),
+    hipError_t e = attr.run([] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&ntt_pass_kernel<LOG_R, EPT, SWZ, SHOUP, CTW>),
                                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((ntt_pass_kernel<LOG_R, EPT, SWZ, SHOUP>), dim3((uint32_t)grid), dim3(threads), lds, stream, P);
+    hipLaunchKernelGGL((ntt_pass_kernel<LOG_R, EPT, SWZ, SHOUP, CTW>), dim3((uint32_t)grid), dim3(threads), lds, stream, P);
     return hipGetLastError();
 }
 static bool swizzle_on() {
     static const bool on = getenv("PLONK_NTT_NO_SWIZZLE") == nullptr;
     return on;
+}
+// the shape launch_one gives the swizzled prepared-constant instantiation — the only one with a folded first pass (coset twiddles)
+static bool swizzled_shoup_shape(const NttTables& T, int log_r, const NttPassParams& P) {
+    return log_r >= 5 && T.use_shoup && ntt_ept() == 4 && P.log_t == 3 && P.tile_pitch == 8 && swizzle_on();
 }
 template <int LOG_R>
 static hipError_t launch_one(const NttPassParams& P, uint64_t grid, uint32_t threads, size_t lds, hipStream_t stream) {
@@ -406,6 +454,7 @@ static hipError_t launch_one(const NttPassParams& P, uint64_t grid, uint32_t thr
     // width a multi-pass plan can contain, ntt_plan_widths)
     if constexpr (LOG_R >= 5) {
         if (ntt_ept() == 4 && P.log_t == 3 && P.tile_pitch == 8 && swizzle_on()) {
+            if (P.tw_shoup != nullptr && P.ctw != nullptr) return launch_one_e<LOG_R, 4, true, true, true>(P, grid, threads, lds, stream);
             if (P.tw_shoup != nullptr) return launch_one_e<LOG_R, 4, true, true>(P, grid, threads, lds, stream);
             return launch_one_e<LOG_R, 4, true>(P, grid, threads, lds, stream);
         }
@@ -567,6 +616,17 @@ int ntt_run(NttTables& T, const NttCall& c, hipStream_t stream) {
             }
             P.ss0 = P.ls0; P.ss1 = P.ls1; P.ss2 = P.ls2; P.s_istride = P.l_astride; P.s_tstride = 1;
             P.tile_pitch = (uint32_t)Tt;
+            // the row table of a coset transform's first pass moves into the butterfly twiddles where the pass has the folded form
+            if (p == 0 && P.pro_rowtab != nullptr && T.coset_twiddles && !interleaved && swizzled_shoup_shape(T, w, P)) {
+                if (sset != nullptr) {
+                    P.ctw = sset->ctw;
+                    P.ctw_qstride = R - 1;
+                } else {
+                    int rc = get_coset_tw(T, log_b0 + ilog2(r_p), w, &P.ctw, stream);
+                    if (rc) return rc;
+                }
+                if (P.ctw != nullptr) P.pro_rowtab = nullptr;
+            }
         } else {
             P.out = c.out;
             P.kstride = M >> w;
@@ -652,6 +712,7 @@ int ntt_run(NttTables& T, const NttCall& c, hipStream_t stream) {
         {
             ProfScope ps_all("ntt_pass_kernel", stream);
             ProfScope ps_w(kNames[w], stream);
+            ProfScope ps_ctw("ntt_pass_coset_tw", stream, P.ctw != nullptr);
             e = launch_pass(w, P, grid, threads, lds, stream);
         }
         if (e != hipSuccess) return plonk_fail(PLONK_ERR_HIP, "ntt pass launch (log_r=%d, grid=%llu, threads=%u, lds=%zu): %s", w,

@@ -102,6 +102,10 @@ struct NttPassParams {
     F29 scale_const;
     TwoLevelScale pro;                    // prologue (first pass) scale, idx = pos
     TwoLevelScale epi;                    // epilogue (last pass) scale, idx = k
+    // Folded first pass (the CTW instantiation): the row scale s^a of a coset transform lives in the butterfly twiddles instead of a product at
+    // load.  Per class, stage after stage: entry 2^sigma - 1 + j = s^(R / 2^(sigma + 1)) * w_(2^(sigma + 1))^j, j < 2^sigma (R - 1 entries).
+    const F29S* ctw;
+    uint64_t ctw_qstride;                 // entries between the tables of consecutive classes (0: one table for all)
 };
 
 __device__ __forceinline__ Fr load_fr(const Fr* p) {
@@ -183,12 +187,14 @@ __device__ __forceinline__ void shoup_tw_load(const F29S* __restrict__ tab, uint
     }
 }
 // The K radix-2 stages s0 .. s0+K-1 on the 2^K elements of one group (v[k] = row a0 + k * 2^s0, lo = the group's low row bits).
-template <int LOG_R, int K, bool FIRST, bool SHOUP>
+// CTW: tw_shoup is the tile's coset twiddle table (NttPassParams::ctw); stage sigma = s0 + ds reads entry 2^sigma - 1 + j, j = lo + kk * h.
+template <int LOG_R, int K, bool FIRST, bool SHOUP, bool CTW = false>
 __device__ __forceinline__ void ntt_butterflies(F29 (&v)[1 << K], int s0, uint32_t lo, const uint32_t* tw_lds, const F29S* __restrict__ tw_shoup,
                                                 const F29Params& fp) {
     constexpr int R = 1 << LOG_R;
     constexpr int RADIX = 1 << K;
     constexpr int TWN = (R / 2 > 0) ? R / 2 : 1;
+    static_assert(!CTW || (SHOUP && !FIRST), "coset twiddles: every stage carries a prepared-constant product");
     const uint32_t h = 1u << s0;
 #pragma unroll
     for (int ds = 0; ds < K; ds++) {
@@ -211,7 +217,8 @@ __device__ __forceinline__ void ntt_butterflies(F29 (&v)[1 << K], int s0, uint32
                 const uint32_t e = (lo + kk * h) << (LOG_R - s0 - ds - 1);
                 if constexpr (SHOUP) {
                     uint32_t cw[20];
-                    shoup_tw_load<LOG_R>(tw_shoup, e, cw);
+                    if constexpr (CTW) shoup_tw_load<NTT_LOG_RMAX>(tw_shoup, (h << ds) - 1 + lo + kk * h, cw);
+                    else shoup_tw_load<LOG_R>(tw_shoup, e, cw);
                     tt = f29_mul_shoup(v[k + span], cw, cw + 9, fp);
                     v[k] = f29_add(x, tt);
                     v[k + span] = f29_sub4p(x, tt, fp);
@@ -243,10 +250,26 @@ __device__ __forceinline__ void ntt_butterflies(F29 (&v)[1 << K], int s0, uint32
 // f29_mul's DOCUMENTED range is 2^259.4 = 23p there; its real requirement is the same x < 2^261, limbs < 2^31, with a result below
 // x * p / 2^261 + p < 2p instead of 1.36p — still below 2^256 for the 8 x 32-bit store and below f29_canon's 2p).  The last pass ends in
 // f29_canon_lazy (< 48p, below 2^261 on both fields).  Host build of this code against Python integers over these ranges: tests/test_fp29_host.py.
+//
+// CONTRACT of the folded first pass (CTW: the coset shift's row scale s^a sits in the butterfly twiddles).  A scale s^a on the inputs of a
+// radix-2 DIT is  F_R(x; s)[k] = F_{R/2}(x_even; s^2)[k] + s * w_R^k * F_{R/2}(x_odd; s^2)[k],  so stage sigma (joining blocks of 2^sigma) multiplies
+// by s^(R / 2^(sigma+1)) * w_(2^(sigma+1))^j instead of w_(2^(sigma+1))^j: the same prepared-constant product, from the class's own table, but no
+// stage is product-free any more (FIRST = false throughout: + 0.75 prepared products per element) and the Montgomery product at load is gone.
+// Entry values E: raw canonical coefficients (< p, normalised by f29_from_sat), zero rows, or the fold sum (< p + 7 * 1.36p = 10.6p, normalised by the
+// load loop).  Values: a butterfly leaves x + t and x + 4p - t with t < 3p (f29_mul_shoup's result; x + 4p - t > 0), so every stage adds at most
+// 4p: the operand of a stage-sigma product is below E + 4p * sigma <= 10.6p + 32p = 42.6p and the tile ends below 10.6p + 4p * 9 = 46.6p — inside
+// 2^261 = 70p (BLS12-381) / 169p (BN254), so f29_mul_shoup and the plane product that follows are in range; the plane product returns
+// < 46.6p * p / 2^261 + p < 1.67p (BLS12-381; 1.28p on BN254), below 2^256 for the re-packed store.  The next pass therefore enters below
+// L = 1.67p instead of 1.6p: its two product-free stages reach L + 6p < 7.67p and its nine stages < 35.7p — still inside f29_canon_lazy's 48p and
+// 2^261.  Limbs: the stages run as non-FIRST steps with the normalisation points of every later step (after ds == 1 and after a step's last
+// stage), the tile is normalised on entry, so a product operand has seen at most one un-normalised f29_add / f29_sub4p: limbs < 2^29 + (2^30 +
+// 2^29) = 2^31; the other operand of that stage's add / sub is below 2^31 as well and x + c4p - t < 2^31 + 2^30 + 2^29 < 2^32 does not wrap.  A
+// normalised value below 2^261 has a top limb below 2^29.  Host build of this chain against Python integers, nine stages from both entry bounds:
+// tests/test_ntt_coset_twiddles_host.py.
 // SHOUP: the butterfly products use the precomputed-quotient multiplier with twiddles fetched from the 80-byte global table (five
 // 128-bit loads per product on the otherwise idle vector-memory pipe; the table is L1-resident) instead of Montgomery products
 // with twiddles from LDS: 143 limb products instead of 171 + 9.
-template <int LOG_R, int K, int EPT, bool FIRST, bool SWZ, bool SHOUP>
+template <int LOG_R, int K, int EPT, bool FIRST, bool SWZ, bool SHOUP, bool CTW = false>
 __device__ __forceinline__ void ntt_step(const LdsTile& tile, const uint32_t* tw_lds, const F29S* __restrict__ tw_shoup, int s0, uint32_t w, uint32_t t,
                                          uint32_t pitch, const F29Params& fp) {
     constexpr int R = 1 << LOG_R;
@@ -263,7 +286,7 @@ __device__ __forceinline__ void ntt_step(const LdsTile& tile, const uint32_t* tw
         const uint32_t fa = sw_fold<SWZ>(a0);
 #pragma unroll
         for (int k = 0; k < RADIX; k++) v[k] = tile.get(((a0 + k * h) ^ fa ^ sw_fold<SWZ>(k * h)) * pitch + t);
-        ntt_butterflies<LOG_R, K, FIRST, SHOUP>(v, s0, lo, tw_lds, tw_shoup, fp);
+        ntt_butterflies<LOG_R, K, FIRST, SHOUP, CTW>(v, s0, lo, tw_lds, tw_shoup, fp);
 #pragma unroll
         for (int k = 0; k < RADIX; k++) tile.put(((a0 + k * h) ^ fa ^ sw_fold<SWZ>(k * h)) * pitch + t, v[k]);
     }
@@ -308,10 +331,14 @@ __device__ __forceinline__ void ntt_steps0123_xlane(const LdsTile& tile, const u
 }
 #endif
 
-template <int LOG_R, int EPT_REQ, bool SWZ = false, bool SHOUP = false>
+// CTW (coset twiddles): the folded first pass of a coset transform — no row-table product at load, all LOG_R stages multiply by the class's
+// table P.ctw (CONTRACT above).  Only the production shape has it: swizzled 8-column tiles, prepared-constant butterflies, R > EPT, a non-last
+// pass whose tile lies in one class (tq = 0).  CTW = false is the code every other transform runs, unchanged.
+template <int LOG_R, int EPT_REQ, bool SWZ = false, bool SHOUP = false, bool CTW = false>
 __global__ void __launch_bounds__(EPT_REQ <= 4 ? 1024 : 512) ntt_pass_kernel(const NttPassParams P) {
     constexpr int R = 1 << LOG_R;
     constexpr int EPT = (R >= EPT_REQ) ? EPT_REQ : R;
+    static_assert(!CTW || (SWZ && SHOUP && R > EPT), "coset twiddles are built for the swizzled prepared-constant shape");
     constexpr int KMAX = (EPT == 8) ? 3 : (EPT == 4) ? 2 : (EPT == 2 ? 1 : 1);
     constexpr int TWN = (R / 2 > 0) ? R / 2 : 1;
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
@@ -375,12 +402,14 @@ __global__ void __launch_bounds__(EPT_REQ <= 4 ? 1024 : 512) ntt_pass_kernel(con
         } else {
             v = f29_from_sat(load_fr(P.in + lbase + (uint64_t)a * P.l_astride + (uint64_t)t * P.l_tstride));
         }
-        if (P.pro_rowtab != nullptr) {
-            v = f29_mul(v, load_f29(P.pro_rowtab + cls * P.rowtab_qstride + a), P.fp);
-        } else if (P.pro.enabled) {
-            const uint64_t pos = (uint64_t)a * P.pa + x0 * P.ps0 + x1 * P.ps1 + (uint64_t)t * P.pt;
-            const F29 s = two_level(P.pro, pos, arr, P.fp);
-            v = f29_mul(v, s, P.fp);
+        if constexpr (!CTW) {
+            if (P.pro_rowtab != nullptr) {
+                v = f29_mul(v, load_f29(P.pro_rowtab + cls * P.rowtab_qstride + a), P.fp);
+            } else if (P.pro.enabled) {
+                const uint64_t pos = (uint64_t)a * P.pa + x0 * P.ps0 + x1 * P.ps1 + (uint64_t)t * P.pt;
+                const F29 s = two_level(P.pro, pos, arr, P.fp);
+                v = f29_mul(v, s, P.fp);
+            }
         }
         const uint32_t row = brev(a, LOG_R);
         tile.put((row ^ sw_fold<SWZ>(row)) * pitch + t, v);
@@ -393,32 +422,34 @@ __global__ void __launch_bounds__(EPT_REQ <= 4 ? 1024 : 512) ntt_pass_kernel(con
         const uint32_t t = u & (T - 1), w = u >> LOG_T;
         constexpr int KREM = LOG_R % KMAX;
         constexpr int SFULL = LOG_R - KREM;          // stages covered by full groups
+        // the butterflies' prepared twiddles: w_R^e for every tile, or the coset table of the tile's class (tq = 0: one class per workgroup)
+        const F29S* const tws = CTW ? P.ctw + (q0 & (((uint64_t)1 << P.cls_log) - 1)) * P.ctw_qstride : P.tw_shoup;
         if constexpr (R <= EPT) {
-            ntt_step<LOG_R, LOG_R, EPT, true, SWZ, SHOUP>(tile, tw_lds, P.tw_shoup, 0, w, t, pitch, P.fp);
+            ntt_step<LOG_R, LOG_R, EPT, true, SWZ, SHOUP>(tile, tw_lds, tws, 0, w, t, pitch, P.fp);
             __syncthreads();
         } else {
             if constexpr (SFULL > 0) {
 #ifdef NTT_XLANE
-                constexpr bool XL = SWZ && EPT == 4 && LOG_R >= 7;       // one group per lane, 8-column tiles: w = u >> 3
+                constexpr bool XL = !CTW && SWZ && EPT == 4 && LOG_R >= 7;       // one group per lane, 8-column tiles: w = u >> 3
 #else
                 constexpr bool XL = false;
 #endif
                 if constexpr (XL) {
 #ifdef NTT_XLANE
-                    ntt_steps0123_xlane<LOG_R, SWZ, SHOUP>(tile, tw_lds, P.tw_shoup, w, t, pitch, P.fp);
+                    ntt_steps0123_xlane<LOG_R, SWZ, SHOUP>(tile, tw_lds, tws, w, t, pitch, P.fp);
 #endif
                 } else {
-                    ntt_step<LOG_R, KMAX, EPT, true, SWZ, SHOUP>(tile, tw_lds, P.tw_shoup, 0, w, t, pitch, P.fp);
+                    ntt_step<LOG_R, KMAX, EPT, !CTW, SWZ, SHOUP, CTW>(tile, tw_lds, tws, 0, w, t, pitch, P.fp);
                 }
                 __syncthreads();
 #pragma unroll 1
                 for (int s = XL ? 2 * KMAX : KMAX; s < SFULL; s += KMAX) {
-                    ntt_step<LOG_R, KMAX, EPT, false, SWZ, SHOUP>(tile, tw_lds, P.tw_shoup, s, w, t, pitch, P.fp);
+                    ntt_step<LOG_R, KMAX, EPT, false, SWZ, SHOUP, CTW>(tile, tw_lds, tws, s, w, t, pitch, P.fp);
                     __syncthreads();
                 }
             }
             if constexpr (KREM != 0) {
-                ntt_step<LOG_R, KREM, EPT, SFULL == 0, SWZ, SHOUP>(tile, tw_lds, P.tw_shoup, SFULL, w, t, pitch, P.fp);
+                ntt_step<LOG_R, KREM, EPT, SFULL == 0 && !CTW, SWZ, SHOUP, CTW>(tile, tw_lds, tws, SFULL, w, t, pitch, P.fp);
                 __syncthreads();
             }
         }

@@ -262,6 +262,7 @@ extern "C" int plonk_set_option(plonk_ctx* ctx, const char* key, int64_t value) 
         ctx->tables.use_shoup = value != 0;
         return PLONK_OK;
     }
+    if (!strcmp(key, "ntt_coset_twiddles")) { ctx->tables.coset_twiddles = value != 0; return PLONK_OK; }   // default 1: the folded first pass of coset transforms (0 = the row-table product at load)
     if (!strcmp(key, "ntt_plane_budget")) {       // tests: BYTES of factor planes this context may hold (< 0: the default); applies from the next transform, frees nothing
         ctx->tables.plane_budget = value < 0 ? NTT_PLANE_BUDGET_DEFAULT : (size_t)value;
         return PLONK_OK;

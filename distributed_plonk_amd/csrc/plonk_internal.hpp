@@ -60,7 +60,7 @@ struct KernelProfiler {       // process-wide; contexts on different host thread
 KernelProfiler& kernel_profiler();
 struct ProfScope {       // RAII: brackets the launches issued in its lifetime
     const char* name; hipStream_t stream; hipEvent_t a = nullptr, b = nullptr; bool on;
-    ProfScope(const char* n, hipStream_t s) : name(n), stream(s), on(kernel_profiler().enabled) {
+    ProfScope(const char* n, hipStream_t s, bool wanted = true) : name(n), stream(s), on(wanted && kernel_profiler().enabled) {
         if (on) { (void)hipEventCreate(&a); (void)hipEventCreate(&b); (void)hipEventRecord(a, stream); }
     }
     ~ProfScope() {
@@ -91,11 +91,14 @@ struct NttTables {
     std::unordered_map<int, F29*> tw_lo_scaled;   // key = log_m (inverse only): w^-e * 2^-log_m
     std::unordered_map<uint64_t, Fr*> planes;     // inter-pass factor planes (see ntt_engine.hip: plane_key)
     std::unordered_map<uint64_t, F29*> rowtabs;   // coset row tables g^(a*r_1)
+    std::unordered_map<uint64_t, F29S*> ctw_tabs; // the same shifts as coset twiddles of the folded first pass (same key)
+    bool coset_twiddles = true;                   // "ntt_coset_twiddles": first passes of coset transforms take their row scale in the butterfly twiddles (ntt_kernels.hpp)
     // first-pass tables of class-decomposed coset evaluations (ntt_engine.hip: get_shift_set), keyed by (shift, log M, log B, first width)
     struct ShiftSet {
         Fr* planes = nullptr;       // [B][M]: w_M^(b*i) * h_q^b            (transforms of two or more passes)
         F29* rowtabs = nullptr;     // [B][R_1]: h_q^(a * r_1)
         F29* foldc = nullptr;       // [B][NTT_MAX_FOLD]: (h_q^M)^u
+        F29S* ctw = nullptr;        // [B][R_1 - 1]: coset twiddles of s_q = h_q^r_1 for the folded first pass (widths >= 5, two or more passes)
         size_t bytes = 0;
     };
     std::unordered_map<std::string, ShiftSet> shift_sets;

@@ -472,7 +472,9 @@ int plonk_debug_field_op(plonk_ctx* ctx, int field, int op, const uint64_t* a, c
  * reduction as tree sums over the bucket grid instead of the running-sum pyramid — faster for one small MSM alone, not beside another context's
  * accumulation: profiles/r04_pin_nop_experiment.txt), "msm_fused_order" (the bucket-size histogram inside the level-2 sort: 1 = for launches of
  * >= 2^23 points (default), 2 = always, 0 = never), "msm_fused_y3", "ntt_shoup" (both curves, default 1: precomputed-quotient butterflies in
- * the NTT passes; 0 = Montgomery butterflies), "ntt_plane_budget" (tests: BYTES of NTT factor planes the context may hold, < 0 = the default of
+ * the NTT passes; 0 = Montgomery butterflies), "ntt_coset_twiddles" (default 1: the first pass of a coset transform — plonk_coset_eval_dev classes
+ * of two or more passes, the whole-vector forward coset NTT — takes its row scale in per-class butterfly twiddles instead of a product at load,
+ * where the pass has the production shape: width >= 5, "ntt_shoup" on; 0 = the row-table product; same results), "ntt_plane_budget" (tests: BYTES of NTT factor planes the context may hold, < 0 = the default of
  * 48 GiB; takes effect at the next transform, frees nothing and keeps what is cached — whole-vector and distributed transforms that get no plane
  * form their factors on the fly, plonk_coset_eval_dev / plonk_fft1_dev_compact fail with PLONK_ERR_HIP), "check_bases" (default 1: plonk_init* verifies that every base is a curve point), "quotient_fuse" (6 = default: the compact kernel; 0-5, 7: other formulations).
  * INTEGRATION.md §6 has the table. */
@@ -518,7 +520,8 @@ int plonk_msm_plan(plonk_ctx* ctx, size_t n, int K, int32_t* out, int n_out);
 int plonk_last_kernel_ms(plonk_ctx* ctx, double* out_ms);
 
 /* Per-kernel timing with HIP events recorded on the context's stream around every kernel launch
- * (off by default).  Names: "ntt_pass_kernel", "ntt_pass_kernel<9>" (per in-LDS size), "ntt_gen_plane", "ntt_gen_epi_plane",
+ * (off by default).  Names: "ntt_pass_kernel", "ntt_pass_kernel<9>" (per in-LDS size), "ntt_pass_coset_tw" (the passes among them that ran
+ * with coset twiddles, option "ntt_coset_twiddles"), "ntt_gen_plane", "ntt_gen_epi_plane",
  * "ntt_gen_shift_plane" (the generators of the inter-pass, output-factor and shared-input first-pass planes: one launch per plane built),
  * "msm_sort" (digits, histograms, scan, both sort levels), "msm_bucket_order", "msm_accumulate_kernel", "msm_accumulate_redo_kernel", "msm_heavy",
  * "msm_reduce", "quotient_evals_kernel", "perm_terms_kernel", "perm_scan_num", "perm_scan_den_final",
