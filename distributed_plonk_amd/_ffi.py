@@ -112,6 +112,10 @@ SIGNATURES = {
                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "plonk_circuit_solve_hints_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "plonk_circuit_schedule_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "plonk_circuit_replay_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint]),
     "plonk_rescue_permute_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "plonk_rescue_merkle_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint]),
     "plonk_rescue_acc_build_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p]),

@@ -25,6 +25,10 @@ Hashing: `rescue_permutation`, `rescue_hash2` and `merkle_root` emit the Rescue 
 do the same for the ternary rescue.Accumulator (membership.py builds the reference's generate_circuit shape from them).  Inputs that are
 already on the device — a rescue.Accumulator's witness_inputs_dev — go into a solve as `d_inputs=` and never visit the host.
 
+Same circuit, next witness: `BuiltCircuit.schedule` records the solver's order of evaluation once (plonk_circuit_schedule_dev),
+`solve_many_dev` replays it for K witnesses in one go (plonk_circuit_replay_dev; each witness bit-identical to solve_dev's), and `setup`
+gives a `circuit.CircuitKey` — permutation and proving key, once — whose `instances(batch)` are what `Prover.prove_dev` takes per witness.
+
 Field constants are Python ints (or sequences of them, one per gate), reduced mod r.  Gate equation and selector order: circuit.py.
 """
 from __future__ import annotations
@@ -36,7 +40,7 @@ import numpy as np
 from . import circuit as _circuit
 from . import fr as _fr
 from .synthetic import NUM_SELECTORS, NUM_WIRE_TYPES
-from .worker import PlonkWorker
+from .worker import REPLAY_FUSE_DEFAULT, PlonkWorker
 
 SELECTOR_INDEX = {**{f"q_lc{i}": i for i in range(4)}, "q_mul0": 4, "q_mul1": 5, **{f"q_hash{i}": 6 + i for i in range(4)}, "q_o": 10, "q_c": 11}
 GIVEN = 0xFFFFFFFF                                    # def_gate of a variable no gate defines
@@ -64,6 +68,7 @@ class BuiltCircuit:
             raise ValueError(f"hint_op of shape {self.hint_op.shape} for {wire_vars.shape[1]} gates")
         self._dev = None                              # (worker, [wire_vars, selector_evals, def_gate(, hint_op)] device buffers)
         self._dev_input_vars = None                   # input_vars as u32 on the same worker, once a solve took d_inputs
+        self._schedule = None                         # the SolveSchedule of the upload, once schedule() recorded it
 
     @property
     def n(self) -> int:
@@ -102,6 +107,98 @@ class BuiltCircuit:
         if self._dev_input_vars is not None:
             self._dev_input_vars.free()
             self._dev_input_vars = None
+        if self._schedule is not None:
+            self._schedule.d_order.free()
+            self._schedule = None
+
+    def _input_vars_dev(self, worker: PlonkWorker):
+        if self._dev_input_vars is None:
+            ids = np.ascontiguousarray(self.input_vars, dtype=np.uint32)
+            self._dev_input_vars = worker.alloc(max(4, ids.nbytes)).upload(ids)
+        return self._dev_input_vars
+
+    def schedule(self, worker: PlonkWorker) -> "SolveSchedule":
+        """The order in which the solver evaluates this circuit's defining gates (plonk_circuit_schedule_dev): a function of the circuit alone,
+        recorded once per upload and kept until close().  Raises circuit.UnsolvableCircuit as solve_dev does."""
+        if worker.curve_name != self.curve:
+            raise ValueError(f"circuit over {self.curve}, worker over {worker.curve_name}")
+        d_vars, d_sel, d_def, *d_hint = self._upload(worker)
+        if self._schedule is None:
+            d_order = worker.alloc(self.n * 4)
+            try:
+                unsolved, levels, evaluations, seg = worker.circuit_schedule_dev(d_vars.ptr, self.n, self.num_vars, d_sel.ptr, d_def.ptr,
+                                                                                 d_hint[0].ptr if d_hint else 0, d_order.ptr)
+                if unsolved >= 0:
+                    raise _circuit.UnsolvableCircuit(unsolved)
+            except BaseException:
+                d_order.free()
+                raise
+            self._schedule = SolveSchedule(d_order, seg, levels, evaluations)
+        return self._schedule
+
+    def solve_many_dev(self, worker: PlonkWorker, inputs=None, public_inputs=None, *, d_inputs: Optional[int] = None, fuse_width: Optional[int] = None,
+                       K: Optional[int] = None) -> "SolvedBatch":
+        """solve_dev for K witnesses of this circuit at once, by replaying its schedule() (plonk_circuit_replay_dev): witness b is bit-identical
+        to what solve_dev gives for inputs[b], public_inputs[b].  inputs: (K, len(input_vars), 4), public_inputs: (K, num_public, 4) Montgomery
+        limbs; d_inputs, instead of `inputs`: a device pointer to the same K x len(input_vars) values, scattered on the device.  K: only needed
+        where neither array tells it.  fuse_width: see PlonkWorker.circuit_replay_dev; the result does not depend on it.  The work is enqueued;
+        SolvedBatch.witness, or any synchronising call, waits for it.  Shape errors are ValueError.  -> SolvedBatch (close() it)."""
+        if worker.curve_name != self.curve:
+            raise ValueError(f"circuit over {self.curve}, worker over {worker.curve_name}")
+        if d_inputs is not None and inputs is not None:
+            raise ValueError("inputs and d_inputs: one of them")
+        num_in = len(self.input_vars)
+        inp = None if inputs is None else np.ascontiguousarray(inputs, dtype=np.uint64)
+        pub = None if public_inputs is None else np.ascontiguousarray(public_inputs, dtype=np.uint64)
+        if inp is not None and (inp.ndim != 3 or inp.shape[1:] != (num_in, 4)):
+            raise ValueError(f"inputs: shape {inp.shape}, expected (K, {num_in}, 4)")
+        if pub is not None and (pub.ndim != 3 or pub.shape[1:] != (self.num_public, 4)):
+            raise ValueError(f"public_inputs: shape {pub.shape}, expected (K, {self.num_public}, 4)")
+        counts = {int(x) for x in (K, None if inp is None else inp.shape[0], None if pub is None else pub.shape[0]) if x is not None}
+        if len(counts) != 1:
+            raise ValueError(f"the number of witnesses: {sorted(counts) or 'not given (inputs, public_inputs or K)'}")
+        K = counts.pop()
+        if K < 1:
+            raise ValueError(f"{K} witnesses")
+        if inp is None and d_inputs is None and num_in:
+            raise ValueError(f"no input values for {num_in} inputs")
+        if pub is None and self.num_public:
+            raise ValueError(f"no public input values for {self.num_public} public inputs")
+        if fuse_width is None:
+            fuse_width = REPLAY_FUSE_DEFAULT
+        if not 0 <= fuse_width < 1 << 32:
+            raise ValueError(f"fuse_width {fuse_width}")
+        sched = self.schedule(worker)
+        d_vars, d_sel, _, *d_hint = self._upload(worker)
+        out = SolvedBatch(worker, self, K, d_vars.ptr, d_sel.ptr)
+        try:
+            if d_inputs is None:
+                witness = np.zeros((K, self.num_vars, 4), dtype=np.uint64)
+                if num_in:
+                    witness[:, self.input_vars] = inp
+                out.d_witness.upload(witness)
+                del witness
+            else:
+                worker.memset_dev(out.d_witness.ptr, 0, K * self.num_vars * 32)
+                ids = self._input_vars_dev(worker)
+                for b in range(K):
+                    worker.circuit_scatter_inputs_dev(ids.ptr, num_in, d_inputs + b * num_in * 32, out.d_witness.ptr + b * self.num_vars * 32, self.num_vars)
+            if self.num_public:
+                out.d_pub.upload(pub)
+            worker.circuit_replay_dev(d_vars.ptr, self.n, self.num_vars, d_sel.ptr, d_hint[0].ptr if d_hint else 0, sched.d_order.ptr, sched.seg, sched.levels,
+                                      out.d_pub.ptr if self.num_public else 0, self.num_public, out.d_witness.ptr, K, fuse_width)
+        except BaseException:
+            out.close()
+            raise
+        return out
+
+    def setup(self, worker: PlonkWorker, k: Optional[np.ndarray] = None) -> _circuit.CircuitKey:
+        """circuit.setup_dev on this circuit's upload: the permutation and the proving key, once for every witness.  The key reads the upload
+        (wire_vars, selector_evals) whenever it makes an instance: close() the key before the circuit."""
+        if worker.curve_name != self.curve:
+            raise ValueError(f"circuit over {self.curve}, worker over {worker.curve_name}")
+        d_vars, d_sel, *_ = self._upload(worker)
+        return _circuit.setup_dev(worker, d_vars.ptr, self.n, self.num_vars, d_sel.ptr, self.num_public, k)
 
     def solve_dev(self, worker: PlonkWorker, inputs=None, public_inputs=None, *, d_inputs: Optional[int] = None) -> "SolvedWitness":
         """inputs: (len(input_vars), 4), public_inputs: (num_public, 4) Montgomery limbs.  The circuit is uploaded once per worker and kept
@@ -129,11 +226,8 @@ class BuiltCircuit:
                 out.d_witness.upload(witness)
                 del witness
             else:
-                if self._dev_input_vars is None:
-                    ids = np.ascontiguousarray(self.input_vars, dtype=np.uint32)
-                    self._dev_input_vars = worker.alloc(max(4, ids.nbytes)).upload(ids)
                 worker.memset_dev(out.d_witness.ptr, 0, self.num_vars * 32)
-                worker.circuit_scatter_inputs_dev(self._dev_input_vars.ptr, len(self.input_vars), d_inputs, out.d_witness.ptr, self.num_vars)
+                worker.circuit_scatter_inputs_dev(self._input_vars_dev(worker).ptr, len(self.input_vars), d_inputs, out.d_witness.ptr, self.num_vars)
             worker.memset_dev(out.d_pub.ptr, 0, n * 32)
             if self.num_public:
                 out.d_pub.upload(pub)
@@ -186,6 +280,44 @@ class SolvedWitness:
 
     def witness(self) -> np.ndarray:
         return self.d_witness.download((self.built.num_vars, 4))
+
+    def close(self):
+        for b in (self.d_witness, self.d_pub):
+            if b.ptr:
+                b.free()
+
+
+class SolveSchedule:
+    """What BuiltCircuit.schedule() records, owned by the BuiltCircuit: d_order (device, u32 [n]) holds the `evaluations` defining gates sorted by
+    (level, cost class, gate); seg (3 levels + 1,) u32: seg[3 L + c] is where class c of level L starts (0 gates and BIT hints, 1 INV / DIV,
+    2 ROOT5), the last word = evaluations.  levels / evaluations: what solve_dev reports for the same circuit."""
+
+    def __init__(self, d_order, seg: np.ndarray, levels: int, evaluations: int):
+        self.d_order, self.seg, self.levels, self.evaluations = d_order, seg, levels, evaluations
+
+    def order(self) -> np.ndarray:
+        """the evaluated gates in replay order -> (evaluations,) u32"""
+        return self.d_order.download((self.evaluations,), dtype=np.uint32)
+
+
+class SolvedBatch:
+    """Device buffers of one solve_many_dev: d_witness (K x num_vars Fr, witness b at byte b * num_vars * 32) and d_pub (K x num_public Fr, the
+    public inputs as given — not padded to the gates), beside the pointers of the circuit's own upload (owned by the BuiltCircuit)."""
+
+    def __init__(self, worker: PlonkWorker, built: BuiltCircuit, K: int, d_wire_vars: int, d_selector_evals: int):
+        self.built, self.K, self.d_wire_vars, self.d_selector_evals = built, K, d_wire_vars, d_selector_evals
+        self.d_witness = worker.alloc(K * built.num_vars * 32)
+        try:
+            self.d_pub = worker.alloc(max(8, K * built.num_public * 32))
+        except BaseException:
+            self.d_witness.free()
+            raise
+
+    def witness(self, b: int) -> np.ndarray:
+        """witness b -> (num_vars, 4); waits for the solve"""
+        if not 0 <= b < self.K:
+            raise IndexError(f"witness {b} of {self.K}")
+        return self.d_witness.download((self.built.num_vars, 4), byte_offset=b * self.built.num_vars * 32)
 
     def close(self):
         for b in (self.d_witness, self.d_pub):

@@ -11,6 +11,8 @@ a witness value per variable, the 13 selector columns and the public inputs.  `p
 
 The work runs on the device: the copy-constraint permutation (plonk_circuit_permutation_dev), witness placement
 (plonk_circuit_witness_dev), the satisfiability check (plonk_circuit_check_dev) and the 13 + 5 inverse NTTs into coefficient form.
+For many witnesses of one circuit `setup_dev` does the witness-independent half once (a `CircuitKey`: permutation, proving key) and
+`CircuitKey.instance` the rest per witness (placement, check); an instance has the attribute names above and borrows the key's buffers.
 Selector order: q_lc 0-3, q_mul 4-5, q_hash 6-9, q_o 10, q_c 11, q_ecc 12.  Field elements are (.., 4) u64 Montgomery limbs.
 """
 from __future__ import annotations
@@ -179,20 +181,132 @@ def preprocess_dev(worker: PlonkWorker, d_wire_vars: int, n: int, num_vars: int,
             gate, pos = w.circuit_check_dev(inst.d_wires.ptr, d_selector_evals, inst.d_pi.ptr, inst.d_idx.ptr, n)
             if gate >= 0 or pos >= 0:
                 raise UnsatisfiedCircuit(gate, pos, n)
-        # proving key: selector and sigma polynomials in coefficient form (n-point iNTTs; ntt_dev consumes its input, so a copy goes in)
-        tmp = w.alloc(n * 32)
-        try:
-            for src, dst, cnt in ((d_selector_evals, inst.d_sel.ptr, NUM_SELECTORS), (inst.d_sig_ev.ptr, inst.d_sig.ptr, NUM_WIRE_TYPES)):
-                for t in range(cnt):
-                    w.memcpy_d2d_async(tmp.ptr, src + t * n * 32, n * 32)
-                    w.ntt_dev(tmp.ptr, dst + t * n * 32, n, True, False)
-            w.sync()
-        finally:
-            tmp.free()
+        _proving_key_polys(w, n, d_selector_evals, inst.d_sig_ev.ptr, inst.d_sel.ptr, inst.d_sig.ptr)
     except BaseException:
         inst.close()
         raise
     return inst
+
+
+def _proving_key_polys(w: PlonkWorker, n: int, d_selector_evals: int, d_sigma_evals: int, d_sel: int, d_sig: int):
+    """proving key: selector and sigma polynomials in coefficient form (n-point iNTTs; ntt_dev consumes its input, so a copy goes in)"""
+    tmp = w.alloc(n * 32)
+    try:
+        for src, dst, cnt in ((d_selector_evals, d_sel, NUM_SELECTORS), (d_sigma_evals, d_sig, NUM_WIRE_TYPES)):
+            for t in range(cnt):
+                w.memcpy_d2d_async(tmp.ptr, src + t * n * 32, n * 32)
+                w.ntt_dev(tmp.ptr, dst + t * n * 32, n, True, False)
+        w.sync()
+    finally:
+        tmp.free()
+
+
+class CircuitInstance:
+    """One witness of a CircuitKey's circuit, placed on the wires: what Prover.prove_dev takes, under PreprocessedCircuit's attribute names.  It
+    owns its wires and d_pi alone; d_id, d_idx, sel_ptrs and sig_ptrs are the key's, which has to outlive it."""
+
+    def __init__(self, key: "CircuitKey"):
+        self.key, self.w, self.n, self.log_n, self.num_inputs, self.k = key, key.w, key.n, key.log_n, key.num_inputs, key.k
+        self.d_id, self.d_idx, self.sel_ptrs, self.sig_ptrs = key.d_id, key.d_idx, key.sel_ptrs, key.sig_ptrs
+        n = self.n
+        self.d_wires = self.w.alloc(NUM_WIRE_TYPES * n * 32)
+        try:
+            self.d_pi = self.w.alloc(n * 32)
+        except BaseException:
+            self.d_wires.free()
+            raise
+        self.wev = [self.d_wires.ptr + i * n * 32 for i in range(NUM_WIRE_TYPES)]
+
+    def public_inputs(self) -> np.ndarray:
+        """`circuit.public_input()`: the num_inputs values (not padded) -> (num_inputs, 4)."""
+        return self.d_pi.download((self.num_inputs, 4))
+
+    def close(self):
+        for b in (self.d_wires, self.d_pi):
+            if b.ptr:
+                b.free()
+
+
+class CircuitKey:
+    """What does not depend on the witness, computed once (setup_dev): the copy-constraint permutation (d_id, d_idx, d_sig_ev) and the proving
+    key (d_sel, d_sig in coefficient form; sel_ptrs / sig_ptrs for Prover.load_key_dev).  d_wire_vars and d_selector_evals stay the caller's
+    and are read again by every instance().  `close()` frees the key's buffers; its instances are closed on their own."""
+
+    def __init__(self, worker: PlonkWorker, d_wire_vars: int, n: int, num_vars: int, d_selector_evals: int, num_inputs: int, k: np.ndarray):
+        self.w, self.n, self.num_vars, self.num_inputs = worker, n, num_vars, num_inputs
+        self.d_wire_vars, self.d_selector_evals = d_wire_vars, d_selector_evals
+        self.log_n = n.bit_length() - 1
+        self.k = np.ascontiguousarray(k, dtype=np.uint64)
+        self._bufs = []
+        try:
+            alloc = lambda nbytes: self._bufs.append(worker.alloc(nbytes)) or self._bufs[-1]
+            self.d_id = alloc(NUM_WIRE_TYPES * n * 32)
+            self.d_idx = alloc(NUM_WIRE_TYPES * n * 8)
+            self.d_sig_ev = alloc(NUM_WIRE_TYPES * n * 32)
+            self.d_sel = alloc(NUM_SELECTORS * n * 32)
+            self.d_sig = alloc(NUM_WIRE_TYPES * n * 32)
+        except BaseException:
+            self.close()
+            raise
+        self.sel_ptrs = [self.d_sel.ptr + t * n * 32 for t in range(NUM_SELECTORS)]
+        self.sig_ptrs = [self.d_sig.ptr + t * n * 32 for t in range(NUM_WIRE_TYPES)]
+
+    def instance(self, d_witness: int, public_inputs=None, check: bool = True) -> CircuitInstance:
+        """The witness at d_witness (num_vars Fr) placed on the wires.  public_inputs: a device pointer to the num_inputs values (a row of
+        SolvedBatch.d_pub), or the values themselves as (num_inputs, 4) host limbs; None without public inputs.  check: run the
+        satisfiability check and raise UnsatisfiedCircuit naming the first failing gate / copy position, as preprocess_dev does."""
+        n, w = self.n, self.w
+        if self.num_inputs and public_inputs is None:
+            raise ValueError(f"no public input values for {self.num_inputs} public inputs")
+        pub = None
+        if self.num_inputs and not isinstance(public_inputs, (int, np.integer)):
+            pub = _fr_array(public_inputs, (4,), "public_inputs").reshape(-1, 4)
+            if pub.shape[0] != self.num_inputs:
+                raise ValueError(f"{pub.shape[0]} public input values for {self.num_inputs} public inputs")
+        inst = CircuitInstance(self)
+        try:
+            w.memset_dev(inst.d_pi.ptr, 0, n * 32)
+            if pub is not None:
+                inst.d_pi.upload(pub)
+            elif self.num_inputs:
+                w.memcpy_d2d_async(inst.d_pi.ptr, int(public_inputs), self.num_inputs * 32)
+            w.circuit_witness_dev(self.d_wire_vars, n, d_witness, self.num_vars, inst.d_wires.ptr)
+            if check:
+                gate, pos = w.circuit_check_dev(inst.d_wires.ptr, self.d_selector_evals, inst.d_pi.ptr, self.d_idx.ptr, n)
+                if gate >= 0 or pos >= 0:
+                    raise UnsatisfiedCircuit(gate, pos, n)
+        except BaseException:
+            inst.close()
+            raise
+        return inst
+
+    def instances(self, batch, check: bool = True):
+        """One instance per witness of a builder.SolvedBatch, in order (a generator: close each instance when its proof is done)."""
+        for b in range(batch.K):
+            yield self.instance(batch.d_witness.ptr + b * self.num_vars * 32, batch.d_pub.ptr + b * self.num_inputs * 32 if self.num_inputs else None, check)
+
+    def close(self):
+        for b in self._bufs:
+            b.free()
+        self._bufs = []
+
+
+def setup_dev(worker: PlonkWorker, d_wire_vars: int, n: int, num_vars: int, d_selector_evals: int, num_inputs: int, k: Optional[np.ndarray] = None) -> CircuitKey:
+    """The witness-independent half of preprocess_dev, once per circuit: the copy-constraint permutation and the 13 + 5 inverse NTTs of the
+    proving key.  d_wire_vars u32 [5][n], d_selector_evals [13][n] Fr: read now and by every CircuitKey.instance, not modified or owned."""
+    if n < 2 or n & (n - 1):
+        raise ValueError(f"gate count {n} is not a power of two >= 2: pad the circuit first (Circuit.pad)")
+    if not 0 <= num_inputs <= n:
+        raise ValueError(f"{num_inputs} public inputs for {n} gates")
+    w = worker
+    key = CircuitKey(w, d_wire_vars, n, num_vars, d_selector_evals, num_inputs, default_k(w.curve_name) if k is None else k)
+    try:
+        w.circuit_permutation_dev(d_wire_vars, n, num_vars, key.k, key.d_id.ptr, key.d_idx.ptr, key.d_sig_ev.ptr)
+        _proving_key_polys(w, n, d_selector_evals, key.d_sig_ev.ptr, key.d_sel.ptr, key.d_sig.ptr)
+    except BaseException:
+        key.close()
+        raise
+    return key
 
 
 def preprocess(worker: PlonkWorker, circuit: Circuit, check: bool = True) -> PreprocessedCircuit:

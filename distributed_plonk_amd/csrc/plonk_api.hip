@@ -93,6 +93,9 @@ struct plonk_ctx {
     unsigned long long* d_bad = nullptr;        // two words for that check's verdict
     Fr* d_rescue = nullptr;                     // Rescue parameters (116 Fr) as last uploaded, and the host bytes they were uploaded from
     std::vector<uint64_t> h_rescue;
+    uint32_t* d_replay_seg = nullptr;           // segment starts of the solve schedule as last uploaded (plonk_circuit_replay_dev), and their host copy
+    size_t replay_seg_cap = 0;                  // words allocated
+    std::vector<uint32_t> h_replay_seg;
 };
 
 // state of the collective order check (comm_order_check, further down)
@@ -218,7 +221,8 @@ extern "C" void plonk_destroy(plonk_ctx* ctx) {
     if (ctx->d_wire) (void)hipFree(ctx->d_wire);
     if (ctx->d_bad) (void)hipFree(ctx->d_bad);
     if (ctx->d_rescue) (void)hipFree(ctx->d_rescue);
-    if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
+    if (ctx->d_replay_seg) (void)hipFree(ctx->d_replay_seg);
+    if (ctx->d_scratch)(void)hipFree(ctx->d_scratch);
     if (ctx->d_scratch2) (void)hipFree(ctx->d_scratch2);
     msm_ws_release(ctx->msm_ws);
     (void)hipEventDestroy(ctx->ev0);
@@ -1288,6 +1292,69 @@ extern "C" int plonk_circuit_solve_hints_dev(plonk_ctx* ctx, const void* d_wire_
                                              uint64_t* levels, uint64_t* evaluations) {
     return circuit_solve_entry(ctx, d_wire_vars, n, num_vars, d_selector_evals, d_pub_input, d_def_gate, d_hint_op, d_witness, unsolved_var, levels, evaluations,
                                "plonk_circuit_solve_hints_dev");
+}
+extern "C" int plonk_circuit_schedule_dev(plonk_ctx* ctx, const void* d_wire_vars, size_t n, size_t num_vars, const void* d_selector_evals,
+                                          const void* d_def_gate, const void* d_hint_op, void* d_order, uint32_t* seg, int64_t* unsolved_var, uint64_t* levels,
+                                          uint64_t* evaluations) {
+    const char* who = "plonk_circuit_schedule_dev";
+    CHECK_CTX(ctx);
+    if (!d_wire_vars || !d_selector_evals || !d_def_gate || !d_order || !seg || !unsolved_var || !levels || !evaluations)
+        return plonk_fail(PLONK_ERR_ARG, "%s: null", who);
+    int rc = circuit_domain(ctx, n, who, nullptr);
+    if (rc) return rc;
+    if (num_vars == 0 || num_vars > 0xFFFFFFFEull)
+        return plonk_fail(PLONK_ERR_ARG, "%s: num_vars = %zu (ids are u32 with one sentinel: 1 .. 2^32 - 2)", who, num_vars);
+    if ((rc = ensure_scratch2(ctx, circuit_schedule_scratch_bytes(n, num_vars, d_hint_op != nullptr)))) return rc;
+    return circuit_schedule_run((const uint32_t*)d_wire_vars, n, num_vars, (const Fr*)d_selector_evals, (const uint32_t*)d_def_gate, (const uint32_t*)d_hint_op,
+                                (uint32_t*)d_order, seg, unsolved_var, levels, evaluations, ctx->d_scratch2, ctx->stream, who);
+}
+// The schedule's segment starts in the context's device buffer, for the fused launches: uploaded when the words differ from the last upload's,
+// from the context's own host copy (the caller's seg is not read after the call returns).
+static int replay_seg(plonk_ctx* ctx, const uint32_t* seg, size_t words) {
+    if (ctx->d_replay_seg && ctx->h_replay_seg.size() == words && !memcmp(ctx->h_replay_seg.data(), seg, words * 4)) return PLONK_OK;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));          // earlier launches read the buffer, an earlier upload may still read the host copy
+    ctx->h_replay_seg.clear();
+    if (ctx->replay_seg_cap < words) {
+        if (ctx->d_replay_seg) (void)hipFree(ctx->d_replay_seg);
+        ctx->d_replay_seg = nullptr; ctx->replay_seg_cap = 0;
+        HIP_TRY(hipMalloc((void**)&ctx->d_replay_seg, words * 4));
+        ctx->replay_seg_cap = words;
+    }
+    ctx->h_replay_seg.assign(seg, seg + words);
+    hipError_t e = hipMemcpyAsync(ctx->d_replay_seg, ctx->h_replay_seg.data(), words * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) { ctx->h_replay_seg.clear(); HIP_TRY(e); }
+    return PLONK_OK;
+}
+// The arguments are checked before the context, on the host alone: none of these refusals needs a device.
+extern "C" int plonk_circuit_replay_dev(plonk_ctx* ctx, const void* d_wire_vars, size_t n, size_t num_vars, const void* d_selector_evals, const void* d_hint_op,
+                                        const void* d_order, const uint32_t* seg, uint64_t levels, const void* d_pub_inputs, size_t num_inputs, void* d_witness,
+                                        size_t K, unsigned fuse_width) {
+    const char* who = "plonk_circuit_replay_dev";
+    if (!d_wire_vars) return plonk_fail(PLONK_ERR_ARG, "%s: d_wire_vars is null", who);
+    if (!d_selector_evals) return plonk_fail(PLONK_ERR_ARG, "%s: d_selector_evals is null", who);
+    if (!d_order) return plonk_fail(PLONK_ERR_ARG, "%s: d_order is null", who);
+    if (!seg) return plonk_fail(PLONK_ERR_ARG, "%s: seg is null", who);
+    if (!d_witness) return plonk_fail(PLONK_ERR_ARG, "%s: d_witness is null", who);
+    if (!d_pub_inputs != !num_inputs)
+        return plonk_fail(PLONK_ERR_ARG, "%s: d_pub_inputs is %s with num_inputs = %zu", who, d_pub_inputs ? "given" : "null", num_inputs);
+    if (num_inputs > n) return plonk_fail(PLONK_ERR_ARG, "%s: num_inputs = %zu for n = %zu gates", who, num_inputs, n);
+    if (K == 0) return plonk_fail(PLONK_ERR_ARG, "%s: K is 0", who);
+    if (levels > n) return plonk_fail(PLONK_ERR_ARG, "%s: levels = %llu for n = %zu gates", who, (unsigned long long)levels, n);
+    for (uint64_t s = 0; s < 3 * levels; s++)
+        if (seg[s + 1] < seg[s])
+            return plonk_fail(PLONK_ERR_ARG, "%s: seg decreases from %u at %llu to %u", who, seg[s], (unsigned long long)s, seg[s + 1]);
+    if (seg[3 * levels] > n) return plonk_fail(PLONK_ERR_ARG, "%s: seg ends at %u for n = %zu gates", who, seg[3 * levels], n);
+    CHECK_CTX(ctx);
+    int rc = circuit_domain(ctx, n, who, nullptr);
+    if (rc) return rc;
+    if (num_vars == 0 || num_vars > 0xFFFFFFFEull)
+        return plonk_fail(PLONK_ERR_ARG, "%s: num_vars = %zu (ids are u32 with one sentinel: 1 .. 2^32 - 2)", who, num_vars);
+    if (K > 0x7FFFFFFFull || (uint64_t)K > ((1ull << 39) - 256) / n)          // one workgroup per witness; seg_len x K lanes in 2^31 - 1 workgroups
+        return plonk_fail(PLONK_ERR_ARG, "%s: K = %zu witnesses of n = %zu gates exceed one launch", who, K, n);
+    if ((rc = replay_seg(ctx, seg, 3 * levels + 1))) return rc;
+    return circuit_replay_run(ctx->curve, (const uint32_t*)d_wire_vars, n, num_vars, (const Fr*)d_selector_evals, (const uint32_t*)d_hint_op,
+                              (const uint32_t*)d_order, ctx->h_replay_seg.data(), ctx->d_replay_seg, levels, (const Fr*)d_pub_inputs, num_inputs, (Fr*)d_witness, K,
+                              fuse_width, ctx->stream, who);
 }
 // The Rescue parameters in the context's device buffer: uploaded when the bytes differ from the last upload.  The copy is ordered on the
 // stream behind the kernels that read the previous parameters, and reads the context's own host copy.

@@ -245,6 +245,15 @@ size_t circuit_solve_scratch_bytes(size_t n, size_t num_vars, bool hints);
 int circuit_solve_run(int curve, const uint32_t* wire_vars, size_t n, size_t num_vars, const Fr* sel, const Fr* pub, const uint32_t* def_gate,
                       const uint32_t* hint_op, Fr* witness, int64_t* unsolved_var, uint64_t* levels, uint64_t* evaluations, void* scratch, hipStream_t stream,
                       const char* who);
+// the solve schedule and its replay (solve_replay.hpp, built in synth.hip).  schedule: order device u32 [n], seg HOST 3n + 1 words; scratch:
+// circuit_schedule_scratch_bytes; synchronises.  replay: seg HOST and d_seg its device copy, 3 * levels + 1 words, non-decreasing, last <= n;
+// pub K x num_inputs, witness K x num_vars; enqueued only.
+size_t circuit_schedule_scratch_bytes(size_t n, size_t num_vars, bool hints);
+int circuit_schedule_run(const uint32_t* wire_vars, size_t n, size_t num_vars, const Fr* sel, const uint32_t* def_gate, const uint32_t* hint_op, uint32_t* order,
+                         uint32_t* seg, int64_t* unsolved_var, uint64_t* levels, uint64_t* evaluations, void* scratch, hipStream_t stream, const char* who);
+int circuit_replay_run(int curve, const uint32_t* wire_vars, size_t n, size_t num_vars, const Fr* sel, const uint32_t* hint_op, const uint32_t* order,
+                       const uint32_t* seg, const uint32_t* d_seg, uint64_t levels, const Fr* pub, size_t num_inputs, Fr* witness, size_t K, unsigned fuse_width,
+                       hipStream_t stream, const char* who);
 // Rescue (rescue_kernels.hpp, built in synth.hip).  params: 116 Fr on the device, the MDS matrix row-major then the 25 round keys; states:
 // [count][4] Fr in place, count > 0; nodes: 2^(log_leaves+1) - 1 Fr in heap order with the leaves filled, 1 <= log_leaves <= 31.  Enqueued only.
 int rescue_permute_run(int curve, const Fr* d_params, Fr* d_states, size_t count, hipStream_t stream, const char* who);

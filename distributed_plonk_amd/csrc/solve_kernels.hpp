@@ -186,33 +186,41 @@ struct SolveScratch {
 
 size_t circuit_solve_scratch_bytes(size_t n, size_t num_vars, bool hints) { return SolveScratch(n, num_vars, hints).total; }
 
-// hint_op NULL: the hint-free solver, kernel for kernel what it was before hints existed.  who: the entry point named in error texts.
-int circuit_solve_run(int curve, const uint32_t* wire_vars, size_t n, size_t num_vars, const Fr* sel, const Fr* pub, const uint32_t* def_gate,
-                      const uint32_t* hint_op, Fr* witness, int64_t* unsolved_var, uint64_t* levels, uint64_t* evaluations, void* scratch, hipStream_t stream,
-                      const char* who) {
+// The solver's device pointers into its scratch area.
+struct SolveBuffers {
+    unsigned long long* flags;
+    uint32_t *keys[2], *vals[2], *hist, *sums, *start, *state, *frontier[2];
+    SolveBuffers(const SolveScratch& L, void* scratch) {
+        char* base = (char*)scratch;
+        flags = (unsigned long long*)base;
+        for (int b = 0; b < 2; b++) {
+            keys[b] = (uint32_t*)(base + L.keys[b]);
+            vals[b] = (uint32_t*)(base + L.vals[b]);
+            frontier[b] = (uint32_t*)(base + L.frontier[b]);
+        }
+        hist = (uint32_t*)(base + L.hist);
+        sums = (uint32_t*)(base + L.sums);
+        start = (uint32_t*)(base + L.start);
+        state = (uint32_t*)(base + L.state);
+    }
+};
+
+// Everything before the level loop, shared by the solver and by the schedule recorder (solve_replay.hpp): validation with its error texts,
+// the state words and sort keys, the first frontier (in B.frontier[0], its size in the flag area) and the consumer lists *sk / *sv with their
+// heads in B.start.  *defined: the number of defining gates; 0 = nothing was sorted and there is nothing to solve.
+static int solve_prepare(const uint32_t* wire_vars, size_t n, size_t num_vars, const Fr* sel, const uint32_t* def_gate, const uint32_t* hint_op,
+                         const SolveScratch& L, const SolveBuffers& B, hipStream_t stream, const char* who, uint64_t* defined, const uint32_t** sk,
+                         const uint32_t** sv) {
     const bool hints = hint_op != nullptr;
-    const SolveScratch L(n, num_vars, hints);
-    char* base = (char*)scratch;
-    unsigned long long* d_flags = (unsigned long long*)base;
-    uint32_t* keys[2] = {(uint32_t*)(base + L.keys[0]), (uint32_t*)(base + L.keys[1])};
-    uint32_t* vals[2] = {(uint32_t*)(base + L.vals[0]), (uint32_t*)(base + L.vals[1])};
-    uint32_t* hist = (uint32_t*)(base + L.hist);
-    uint32_t* sums = (uint32_t*)(base + L.sums);
-    uint32_t* start = (uint32_t*)(base + L.start);
-    uint32_t* state = (uint32_t*)(base + L.state);
-    uint32_t* frontier[2] = {(uint32_t*)(base + L.frontier[0]), (uint32_t*)(base + L.frontier[1])};
+    unsigned long long* d_flags = B.flags;
+    uint32_t* state = B.state;
     const uint64_t N = L.count;
     const uint32_t sentinel = (uint32_t)num_vars;        // num_vars <= 2^32 - 2: larger than every id, and not SOLVE_NONE
-    const FrParams& P = fr_params(curve);
     const uint32_t var_tiles = circ_grid_of(num_vars, CIRC_TILE);
     unsigned long long h[SOLVE_F_HINT_WORDS];
     const size_t flag_words = hints ? SOLVE_F_HINT_WORDS : SOLVE_F_WORDS;
-    SolveExponent e_inv, e_root5;
-    if (hints && !solve_exponents(P, &e_inv, &e_root5)) return plonk_fail(PLONK_ERR_ARG, "%s: 5 divides r - 1, ROOT5 is not defined on this field", who);
     int rc;
-    *unsolved_var = -1;
-    *levels = 0;
-    *evaluations = 0;
+    *defined = 0;
     {
         ProfScope ps("solve_setup", stream);
         // flags: the minima start at all-ones, the three counters at zero
@@ -260,24 +268,52 @@ int circuit_solve_run(int curve, const uint32_t* wire_vars, size_t n, size_t num
         if (hints && h[SOLVE_F_STRAY] != CIRC_NONE)
             return plonk_fail(PLONK_ERR_ARG, "%s: hint_op is not zero at gate %llu, which defines no variable", who, h[SOLVE_F_STRAY]);
         if (h[SOLVE_F_DEFINED] == 0) return PLONK_OK;
-        HIP_TRY(hipMemsetAsync(start, 0xFF, num_vars * 4, stream));
+        *defined = h[SOLVE_F_DEFINED];
+        HIP_TRY(hipMemsetAsync(B.start, 0xFF, num_vars * 4, stream));
         if (hints)
             hipLaunchKernelGGL(solve_hint_keys_kernel, dim3(circ_grid_of(n, CIRC_THREADS)), dim3(CIRC_THREADS), 0, stream, wire_vars, def_gate, sel, hint_op, (uint64_t)n,
-                               sentinel, state, keys[1], frontier[0], d_flags + SOLVE_F_HCOUNT);
+                               sentinel, state, B.keys[1], B.frontier[0], d_flags + SOLVE_F_HCOUNT);
         else
             hipLaunchKernelGGL(solve_keys_kernel, dim3(circ_grid_of(n, CIRC_THREADS)), dim3(CIRC_THREADS), 0, stream, wire_vars, def_gate, sel, (uint64_t)n, sentinel, state,
-                               keys[1], frontier[0], d_flags + SOLVE_F_COUNT0);
+                               B.keys[1], B.frontier[0], d_flags + SOLVE_F_COUNT0);
         if ((rc = circ_launch_status("solve_keys"))) return rc;
     }
-    const uint32_t* sk = keys[1];
-    const uint32_t* sv = nullptr;
+    *sk = B.keys[1];
+    *sv = nullptr;
     {
         ProfScope ps("solve_sort", stream);
-        if ((rc = circ_radix_sort(&sk, &sv, N, circ_radix_passes((uint64_t)num_vars + 1), keys, vals, hist, sums, stream))) return rc;
-        hipLaunchKernelGGL(solve_heads_kernel, dim3(circ_grid_of(N, CIRC_THREADS)), dim3(CIRC_THREADS), 0, stream, sk, N, sentinel, start);
+        if ((rc = circ_radix_sort(sk, sv, N, circ_radix_passes((uint64_t)num_vars + 1), B.keys, B.vals, B.hist, B.sums, stream))) return rc;
+        hipLaunchKernelGGL(solve_heads_kernel, dim3(circ_grid_of(N, CIRC_THREADS)), dim3(CIRC_THREADS), 0, stream, *sk, N, sentinel, B.start);
         if ((rc = circ_launch_status("solve_heads"))) return rc;
     }
-    const uint64_t defined = h[SOLVE_F_DEFINED];
+    return PLONK_OK;
+}
+
+// hint_op NULL: the hint-free solver, kernel for kernel what it was before hints existed.  who: the entry point named in error texts.
+int circuit_solve_run(int curve, const uint32_t* wire_vars, size_t n, size_t num_vars, const Fr* sel, const Fr* pub, const uint32_t* def_gate,
+                      const uint32_t* hint_op, Fr* witness, int64_t* unsolved_var, uint64_t* levels, uint64_t* evaluations, void* scratch, hipStream_t stream,
+                      const char* who) {
+    const bool hints = hint_op != nullptr;
+    const SolveScratch L(n, num_vars, hints);
+    const SolveBuffers B(L, scratch);
+    unsigned long long* d_flags = B.flags;
+    uint32_t* const start = B.start;
+    uint32_t* const state = B.state;
+    uint32_t* const* frontier = B.frontier;
+    const uint64_t N = L.count;
+    const FrParams& P = fr_params(curve);
+    const uint32_t var_tiles = circ_grid_of(num_vars, CIRC_TILE);
+    SolveExponent e_inv, e_root5;
+    if (hints && !solve_exponents(P, &e_inv, &e_root5)) return plonk_fail(PLONK_ERR_ARG, "%s: 5 divides r - 1, ROOT5 is not defined on this field", who);
+    int rc;
+    *unsolved_var = -1;
+    *levels = 0;
+    *evaluations = 0;
+    uint64_t defined = 0;
+    const uint32_t* sk = nullptr;
+    const uint32_t* sv = nullptr;
+    if ((rc = solve_prepare(wire_vars, n, num_vars, sel, def_gate, hint_op, L, B, stream, who, &defined, &sk, &sv))) return rc;
+    if (!defined) return PLONK_OK;
     uint64_t done = 0, depth = 0;
     if (hints) {
         // Per level: class 0 (gates, BIT), class 1 (INV, DIV) and class 2 (ROOT5) each in a launch of its own over its own list; all three read
@@ -339,3 +375,5 @@ int circuit_solve_run(int curve, const uint32_t* wire_vars, size_t n, size_t num
     }
     return PLONK_OK;
 }
+
+#include "solve_replay.hpp"

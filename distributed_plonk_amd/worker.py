@@ -15,6 +15,9 @@ from . import _ffi
 from ._ffi import FftWorkload, MsmWorkload, PlonkError, check  # noqa: F401
 
 
+REPLAY_FUSE_DEFAULT = 256                             # PLONK_REPLAY_FUSE_DEFAULT of include/plonk_hip.h
+
+
 def _u64(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.uint64)
 
@@ -427,6 +430,27 @@ class PlonkWorker:
         check(self.lib.plonk_circuit_solve_hints_dev(self.ctx, d_wire_vars, n, num_vars, d_selector_evals, d_pub_input, d_def_gate, d_hint_op or None, d_witness,
                                                      C.byref(unsolved), C.byref(levels), C.byref(evals)))
         return unsolved.value, levels.value, evals.value
+
+    def circuit_schedule_dev(self, d_wire_vars: int, n: int, num_vars: int, d_selector_evals: int, d_def_gate: int, d_hint_op: int, d_order: int):
+        """The solver's schedule of a circuit, recorded without a witness (plonk_circuit_schedule_dev): d_order (u32 [n]) receives the evaluated
+        gates sorted by (level, cost class, gate) -> (unsolved_var or -1, levels, evaluations, seg); seg: (3 levels + 1,) u32 segment starts,
+        seg[3 L + c] for class c of level L, the last word = evaluations.  Synchronises."""
+        unsolved, levels, evals = C.c_int64(0), C.c_uint64(0), C.c_uint64(0)
+        seg = np.zeros(3 * n + 1, dtype=np.uint32)
+        check(self.lib.plonk_circuit_schedule_dev(self.ctx, d_wire_vars or None, n, num_vars, d_selector_evals or None, d_def_gate or None, d_hint_op or None,
+                                                  d_order or None, _ptr(seg), C.byref(unsolved), C.byref(levels), C.byref(evals)))
+        return unsolved.value, levels.value, evals.value, seg[:3 * levels.value + 1].copy()
+
+    def circuit_replay_dev(self, d_wire_vars: int, n: int, num_vars: int, d_selector_evals: int, d_hint_op: int, d_order: int, seg: np.ndarray, levels: int,
+                           d_pub_inputs: int, num_inputs: int, d_witness: int, K: int, fuse_width: int = REPLAY_FUSE_DEFAULT):
+        """K witnesses (d_witness: K x num_vars Fr, the given variables in place) solved from a recorded schedule (plonk_circuit_replay_dev);
+        d_pub_inputs: K x num_inputs Fr or 0; seg: at least 3 levels + 1 words.  fuse_width: runs of segments of at most that many gates go
+        into one launch with a workgroup per witness, 0 = one launch per segment.  Enqueued on the context's stream, not synchronised."""
+        seg = np.ascontiguousarray(seg, dtype=np.uint32)
+        if seg.ndim != 1 or seg.shape[0] < 3 * levels + 1:
+            raise ValueError(f"seg: shape {seg.shape} for {levels} levels, expected at least ({3 * levels + 1},)")
+        check(self.lib.plonk_circuit_replay_dev(self.ctx, d_wire_vars or None, n, num_vars, d_selector_evals or None, d_hint_op or None, d_order or None,
+                                                _ptr(seg), levels, d_pub_inputs or None, num_inputs, d_witness or None, K, fuse_width))
 
     # ------------------------------------------------------------------ Rescue (distributed_plonk_amd/rescue.py)
     def rescue_permute_dev(self, params: Optional[np.ndarray], d_states: int, count: int):

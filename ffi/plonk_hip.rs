@@ -30,6 +30,7 @@ pub const PLONK_ERR_EXCHANGE: c_int = -5;
 pub const PLONK_COMM_ID_BYTES: usize = 128;
 /// integers filled by `plonk_msm_plan` (the PLONK_MSM_PLAN_* enum of include/plonk_hip.h)
 pub const PLONK_MSM_PLAN_FIELDS: usize = 28;
+pub const PLONK_REPLAY_FUSE_DEFAULT: c_uint = 256;
 
 /// utils.rs:3-8 / hello_world.capnp:8-13
 #[repr(C)]
@@ -164,6 +165,12 @@ extern "C" {
     pub fn plonk_circuit_solve_hints_dev(ctx: *mut plonk_ctx, d_wire_vars: *const c_void, n: usize, num_vars: usize, d_selector_evals: *const c_void,
                                          d_pub_input: *const c_void, d_def_gate: *const c_void, d_hint_op: *const c_void, d_witness: *mut c_void,
                                          unsolved_var: *mut i64, levels: *mut u64, evaluations: *mut u64) -> c_int;
+    pub fn plonk_circuit_schedule_dev(ctx: *mut plonk_ctx, d_wire_vars: *const c_void, n: usize, num_vars: usize, d_selector_evals: *const c_void,
+                                      d_def_gate: *const c_void, d_hint_op: *const c_void, d_order: *mut c_void, seg: *mut u32, unsolved_var: *mut i64,
+                                      levels: *mut u64, evaluations: *mut u64) -> c_int;
+    pub fn plonk_circuit_replay_dev(ctx: *mut plonk_ctx, d_wire_vars: *const c_void, n: usize, num_vars: usize, d_selector_evals: *const c_void,
+                                    d_hint_op: *const c_void, d_order: *const c_void, seg: *const u32, levels: u64, d_pub_inputs: *const c_void,
+                                    num_inputs: usize, d_witness: *mut c_void, k: usize, fuse_width: c_uint) -> c_int;
     pub fn plonk_rescue_permute_dev(ctx: *mut plonk_ctx, params: *const u64, d_states: *mut c_void, count: usize) -> c_int;
     pub fn plonk_rescue_merkle_dev(ctx: *mut plonk_ctx, params: *const u64, d_nodes: *mut c_void, log_leaves: c_uint) -> c_int;
     pub fn plonk_rescue_acc_build_dev(ctx: *mut plonk_ctx, params: *const u64, d_elems: *const c_void, count: usize, height: c_uint, d_nodes: *mut c_void) -> c_int;

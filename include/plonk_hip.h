@@ -375,6 +375,35 @@ int plonk_circuit_solve_dev(plonk_ctx* ctx, const void* d_wire_vars, size_t n, s
 int plonk_circuit_solve_hints_dev(plonk_ctx* ctx, const void* d_wire_vars, size_t n, size_t num_vars, const void* d_selector_evals,
                                   const void* d_pub_input, const void* d_def_gate, const void* d_hint_op, void* d_witness, int64_t* unsolved_var,
                                   uint64_t* levels, uint64_t* evaluations);
+/* The solver's schedule, recorded once per circuit: which gate is evaluated in which level depends on wire_vars, selector_evals, def_gate and
+ * hint_op alone, not on the witness.  The same validation as plonk_circuit_solve_hints_dev with the same error texts (under this entry's name);
+ * hint_op NULL: no hints.  The levels are then walked structurally — no field value is read or written, no witness or public input is needed —
+ * and every defining gate gets the key 3L + c: L its level, c its cost class (0 an ordinary gate or a BIT hint, 1 INV / DIV, 2 ROOT5; without
+ * hints class 0 only).  The stable radix sort of (key, gate) gives
+ *   d_order  u32 [n], device: d_order[0 .. *evaluations) = the evaluated gates sorted by (L, c, gate)
+ *   seg      HOST, 3n + 1 words of which 3 * *levels + 1 are written: seg[3L + c] = the first slot of that segment, seg[3 * *levels] = *evaluations
+ * a function of the circuit alone, whichever lane appended first during the walk.  *unsolved_var, *levels, *evaluations: what the solver
+ * reports for the same circuit.  Scratch: the solver's and 4n + 1 u32.  Synchronises. */
+int plonk_circuit_schedule_dev(plonk_ctx* ctx, const void* d_wire_vars, size_t n, size_t num_vars, const void* d_selector_evals, const void* d_def_gate,
+                               const void* d_hint_op, void* d_order, uint32_t* seg, int64_t* unsolved_var, uint64_t* levels, uint64_t* evaluations);
+/* fuse_width of plonk_circuit_replay_dev unless the caller has a reason for another (profiles/solve_replay.txt) */
+#define PLONK_REPLAY_FUSE_DEFAULT 256
+/* K witnesses solved from a recorded schedule (d_order, seg, levels of plonk_circuit_schedule_dev for the same d_wire_vars, d_selector_evals and
+ * d_hint_op).  d_witness: K x num_vars Fr, witness b at d_witness + b * num_vars * 32 — what plonk_circuit_witness_dev and
+ * plonk_circuit_check_dev take — with the given variables in place and zero elsewhere; d_pub_inputs: K x num_inputs Fr (NULL iff num_inputs = 0),
+ * the public input of witness b at gate g < num_inputs is pub[b][g], 0 at every other gate.  Every evaluated gate goes through the solver's own
+ * value code, so witness b is bit-identical to what plonk_circuit_solve*_dev writes for the same inputs.  No atomics, no sort, no host read and
+ * no synchronisation between launches; the launches are chosen from seg alone:
+ *   wide    one launch per non-empty segment, seg_len x K lanes
+ *   fused   one launch for a maximal run of consecutive segments of at most fuse_width gates each (when it holds more than one non-empty
+ *           segment): workgroup b walks the run for witness b, its lanes striding over each segment, a barrier where the level changes
+ * fuse_width = 0 never fuses.  The result does not depend on fuse_width.  PLONK_ERR_ARG naming the argument, checked on the host before the
+ * context is touched: a NULL pointer, d_pub_inputs given without num_inputs or the reverse, num_inputs > n, K = 0, levels > n, seg decreasing or
+ * seg[3 * levels] > n.  An entry of d_order >= n is skipped; a schedule of another circuit is not defended against.  seg is copied; returns once
+ * the work is enqueued on the context's stream. */
+int plonk_circuit_replay_dev(plonk_ctx* ctx, const void* d_wire_vars, size_t n, size_t num_vars, const void* d_selector_evals, const void* d_hint_op,
+                             const void* d_order, const uint32_t* seg, uint64_t levels, const void* d_pub_inputs, size_t num_inputs, void* d_witness, size_t K,
+                             unsigned fuse_width);
 /* The Rescue permutation on the device, the one builder.py's rescue_permutation proves: state s in Fr^4, alpha = 5, 12 rounds (jellyfish's
  * structure),
  *   s <- s + K[0];   12 times:  s <- M (s_j^(1/5))_j + K[2i+1],   s <- M (s_j^5)_j + K[2i+2]        x^(1/5) = x^d, d = 5^-1 mod (r - 1); 0 -> 0

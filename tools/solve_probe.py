@@ -14,6 +14,14 @@ warm-up (it also sizes the context's scratch); the others give the median, in mi
 yardstick: `inv` and `bits` replace every third round by x <- 1 / x or x <- bit (round mod 254) of x, `root5` alternates x <- x^5 + c y^5 + k
 and x <- x^(1/5), Rescue-like.  A level of the hinted chains holds hints only or gates only, so the time of a hint level is what is left
 of `levels` after the gate levels at the hint-free run's time per level.  Without --hints the output is what it was.
+
+    python tools/solve_probe.py --replay 16 [--height 32] [--members 50] [--fuse-widths 0 64 256 1024] [--reps 5]
+
+--replay K runs another measurement instead: K witnesses of membership.membership_circuit(curve, height, members) over one accumulator,
+their inputs gathered on the device.  K sequential solve_dev calls against one plonk_circuit_schedule_dev and one solve_many_dev per fuse
+width (plonk_circuit_replay_dev), and K preprocess calls against one setup() and K instances: host clock around work that ends in a
+synchronise, the variants alternating within a repetition, median (min .. max) of at least 5 repetitions after a warm-up that also
+compares the replayed witness with the solved one (profiles/solve_replay.txt).
 """
 import argparse
 import json
@@ -103,8 +111,97 @@ def one_size(w: PlonkWorker, log_n: int, depth: int, reps: int, hints=None) -> d
                 ms={k: round(v, 3) for k, v in out.items()})
 
 
+def replay_probe(w: PlonkWorker, height: int, m: int, K: int, reps: int, widths) -> dict:
+    """K witnesses of membership_circuit(curve, height, m) over one accumulator, host clock around work that ends in a synchronise, the variants
+    alternating within each repetition: K x solve_dev against schedule + solve_many_dev per fuse width, K x preprocess against setup + K instances."""
+    import numpy as np
+    from distributed_plonk_amd import rescue as RS
+    from distributed_plonk_amd.membership import membership_circuit
+    built = membership_circuit(w.curve_name, height, m)
+    n, rows, count = built.n, 2 + 4 * height, m * K
+    d_el = w.alloc(count * 32)
+    w.synth_fr(height, d_el.ptr, count)
+    acc = RS.Accumulator(w, RS.RescueParams.default(w.curve_name), d_el.download((count, 4)), height)
+    d_el.free()
+    roots = np.ascontiguousarray(np.broadcast_to(acc.root.reshape(1, 1, 4), (K, 1, 4)))
+    d_all = w.alloc(K * rows * m * 32)
+    for b in range(K):
+        buf = acc.witness_inputs_dev(range(b * m, (b + 1) * m))
+        w.memcpy_d2d(d_all.ptr + b * rows * m * 32, buf.ptr, rows * m * 32)
+        buf.free()
+    at = lambda b: d_all.ptr + b * rows * m * 32
+    times = {}
+
+    def timed(name, fn):
+        w.sync()
+        t0 = time.perf_counter()
+        out = fn()
+        w.sync()
+        times.setdefault(name, []).append((time.perf_counter() - t0) * 1e3)
+        return out
+
+    def solve_each(keep_last):
+        last = None
+        for b in range(K):
+            s = built.solve_dev(w, public_inputs=roots[b], d_inputs=at(b))
+            if keep_last and b == K - 1:
+                last = s.witness()
+            s.close()
+        return last
+
+    def record():
+        d_vars, d_sel, d_def, *d_hint = built._upload(w)
+        d_order = w.alloc(n * 4)
+        try:
+            return w.circuit_schedule_dev(d_vars.ptr, n, built.num_vars, d_sel.ptr, d_def.ptr, d_hint[0].ptr if d_hint else 0, d_order.ptr)[1:3]
+        finally:
+            d_order.free()
+
+    def replay(width):
+        batch = built.solve_many_dev(w, public_inputs=roots, d_inputs=d_all.ptr, fuse_width=width)
+        w.sync()
+        return batch
+
+    def preprocess_each():
+        for b in range(K):
+            built.preprocess(w, public_inputs=roots[b], d_inputs=at(b)).close()
+
+    def setup_and_instances():
+        key = built.setup(w)
+        batch = built.solve_many_dev(w, public_inputs=roots, d_inputs=d_all.ptr)
+        for inst in key.instances(batch):
+            inst.close()
+        batch.close()
+        key.close()
+
+    try:
+        built.schedule(w)
+        levels = evaluations = 0
+        for rep in range(reps + 1):
+            want = timed("solve_dev x K", lambda: solve_each(rep == 0))            # the warm-up also compares the results
+            levels, evaluations = timed("schedule", record)
+            for width in widths:
+                batch = timed(f"solve_many_dev fuse_width={width}", lambda: replay(width))
+                if want is not None:
+                    assert np.array_equal(batch.witness(K - 1), want), f"fuse_width {width}: the replayed witness differs from the solved one"
+                batch.close()
+            timed("preprocess x K", preprocess_each)
+            timed("setup + solve_many_dev + K instances", setup_and_instances)
+    finally:
+        d_all.free()
+        acc.close()
+        built.close()
+        w.trim()
+    stat ={k: dict(median=round(statistics.median(v[1:]), 3), min=round(min(v[1:]), 3), max=round(max(v[1:]), 3)) for k, v in times.items()}
+    return dict(curve=w.curve_name, height=height, m=m, K=K, n=n, num_vars=built.num_vars, levels=levels, evaluations=evaluations, reps=reps, ms=stat)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--replay", type=int, default=0, metavar="K", help="time K witnesses of the membership circuit: solve_dev x K against schedule + solve_many_dev")
+    ap.add_argument("--height", type=int, default=32)
+    ap.add_argument("--members", type=int, default=50)
+    ap.add_argument("--fuse-widths", type=int, nargs="+", default=[0, 64, 256, 1024])
     ap.add_argument("--log-n", type=int, nargs="+", default=[22, 24])
     ap.add_argument("--curve", default="bn254", choices=["bn254", "bls12_381"])
     ap.add_argument("--reps", type=int, default=3)
@@ -113,6 +210,14 @@ def main():
     a = ap.parse_args()
     w = PlonkWorker(me=0, device=0, curve=a.curve)
     try:
+        if a.replay:
+            r = replay_probe(w, a.height, a.members, a.replay, max(a.reps, 5), a.fuse_widths)
+            print(f"membership_circuit({a.curve}, {a.height}, {a.members}): n = {r['n']}, {r['levels']} levels, {r['evaluations']} evaluations; K = {a.replay} witnesses, "
+                  f"median (min .. max) of {r['reps']} repetitions after a warm-up, ms")
+            for name, s in r["ms"].items():
+                print(f"  {name:40s} {s['median']:10.3f}  ({s['min']:.3f} .. {s['max']:.3f})")
+            print(json.dumps(r), flush=True)
+            return
         for log_n in a.log_n:
             r = one_size(w, log_n, a.depth, a.reps)
             ms = r["ms"]
