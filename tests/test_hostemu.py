@@ -83,6 +83,13 @@ def test_poly_kernels(emu_env):
     _run_gpu_tests(emu_env, ["tests/test_gpu_polyops.py"], k="not valid_permutation_closes and not full_size")
 
 
+def test_poly_kernel_edges(emu_env):
+    """tests/test_gpu_polyops_edges.py, all of it: the cases above 2^21 elements (two scan tiles per lane of the scans' top kernel, the second trip
+    of the evaluation's final sum, three division tiles per lane), the tile seams, the extreme values, roots of unity, a vanishing numerator and
+    the class interleave."""
+    _run_gpu_tests(emu_env, ["tests/test_gpu_polyops_edges.py"])
+
+
 def test_prover_and_verifier_on_emulated_device(emu_env):
     """The five rounds on the (emulated) device against the oracle prover, and device proofs accepted by the trapdoor verifier."""
     _run_gpu_tests(emu_env, ["tests/test_gpu_prover.py"], k="rounds_match_oracle and (3-False or 6-True) or real_transcript and bn254 or rejects_unsatisfied "
