@@ -25,6 +25,11 @@ Hashing: `rescue_permutation`, `rescue_hash2` and `merkle_root` emit the Rescue 
 do the same for the ternary rescue.Accumulator (membership.py builds the reference's generate_circuit shape from them).  Inputs that are
 already on the device — a rescue.Accumulator's witness_inputs_dev — go into a solve as `d_inputs=` and never visit the host.
 
+Curve points: a point is a pair (x_ids, y_ids) on the twisted Edwards curve embedded in Fr (edwards.py: Baby Jubjub, Jubjub), whose complete
+addition law needs no case distinction and hence no selector of its own — `point_add` (9 gates), `point_double`, `point_select`, `point_neg`,
+`enforce_on_curve`, `to_bits_strict` (every bit of the canonical residue), `scalar_mul`, `fixed_base_mul` and `schnorr_verify` are composed
+from `mul`, `mul_add`, `lc` and `div`; edwards.py computes the same group on the device and `edwards.schnorr_circuit` builds the circuit.
+
 Same circuit, next witness: `BuiltCircuit.schedule` records the solver's order of evaluation once (plonk_circuit_schedule_dev),
 `solve_many_dev` replays it for K witnesses in one go (plonk_circuit_replay_dev; each witness bit-identical to solve_dev's), and `setup`
 gives a `circuit.CircuitKey` — permutation and proving key, once — whose `instances(batch)` are what `Prover.prove_dev` takes per witness.
@@ -527,6 +532,11 @@ class CircuitBuilder:
         nbits = self._nbits(nbits, self.field.p.bit_length() - 1)
         x = self._var(x)
         bits = [self.bit(x, k) for k in range(nbits)]
+        return self._recompose(bits, x)
+
+    def _recompose(self, bits: list, x):
+        """x = sum 2^i bits[i] (mod r) enforced; -> bits"""
+        nbits = len(bits)
         # Horner from the top: acc <- 2^j acc + (the next j bits), 3 bits per gate; the last gate has x on wire 4
         acc, at = None, nbits
         while True:
@@ -658,6 +668,183 @@ class CircuitBuilder:
             mid = self.sub(self.lc([cur, sib1, sib2, l], [1, 1, 1, -1]), r)
             cur = self.rescue_hash3(l, mid, r, prm)
         return cur
+
+    # ------------------------------------------------------------------ the embedded Edwards curve (edwards.py: the same group on the device)
+    # A point is a pair (x_ids, y_ids).  E: a x^2 + y^2 = 1 + d x^2 y^2 with a a square and d a non-square, so for points ON E no denominator
+    # below is zero and one formula serves P + Q, P + P, P - P, the identity (0, 1) and the points of small order.  The gadgets are gates the
+    # builder already has (mul, mul_add, lc, div): no selector of their own.  The quotients are div gates, checked by y * b = a: a zero
+    # denominator — possible only for a point off E — leaves the circuit unsatisfied unless the numerator vanishes too, so a gadget's
+    # points must be on E: a constant, enforce_on_curve'd, checked outside the circuit (a public key), or the output of a gadget.
+    def _edwards_params(self, prm):
+        from .edwards import EdwardsParams
+        if prm is None:
+            return EdwardsParams.default(self.curve)
+        if not isinstance(prm, EdwardsParams) or prm.curve != self.curve:
+            raise ValueError(f"prm: an edwards.EdwardsParams over {self.curve}")
+        return prm
+
+    def _points(self, points, others=()):
+        """pairs checked, and every id of `points` and `others` broadcast to one length -> (list of (x, y), list of the others)"""
+        flat = []
+        for p in points:
+            if not isinstance(p, (tuple, list)) or len(p) != 2:
+                raise ValueError("a point is a pair (x_ids, y_ids)")
+            flat += [p[0], p[1]]
+        vs = self._same_length(flat + list(others))
+        k = len(points)
+        return [(vs[2 * i], vs[2 * i + 1]) for i in range(k)], vs[2 * k:]
+
+    def point_constant(self, x: int, y: int, prm=None):
+        """The constant point (x, y) of E as a pair of constant variables (at most 2 gates, shared with equal constants)."""
+        prm = self._edwards_params(prm)
+        p = self.field.p
+        x, y = int(x) % p, int(y) % p
+        if (prm.a * x * x + y * y - 1 - prm.d * x * x * y * y) % p:
+            raise ValueError("point_constant: not on the curve")
+        return self.constant(x), self.constant(y)
+
+    def point_add(self, p, q, prm=None):
+        """p + q by the complete law: x3 = (x1 y2 + y1 x2) / (1 + d t), y3 = (y1 y2 - a x1 x2) / (1 - d t), t = x1 x2 y1 y2.  Per instance
+        9 gates (mul_add, three mul, three lc, two div) in 4 levels."""
+        prm = self._edwards_params(prm)
+        ((x1, y1), (x2, y2)), _ = self._points([p, q])
+        nx = self.mul_add(x1, y2, y1, x2)
+        xx, yy = self.mul(x1, x2), self.mul(y1, y2)
+        t = self.mul(xx, yy)
+        ny = self.lc([yy, xx], [1, -prm.a])
+        dx, dy = self.lc([t], [prm.d], const=1), self.lc([t], [-prm.d], const=1)
+        return self.div(nx, dx), self.div(ny, dy)
+
+    def point_double(self, p, prm=None):
+        """2 p for p ON E, where t = x^2 y^2 need not be formed: x3 = 2 x y / (a x^2 + y^2), y3 = (y^2 - a x^2) / (2 - a x^2 - y^2).  Per
+        instance 8 gates (three mul, three lc, two div) in 3 levels.  (point_add(p, p) is the law itself and asks nothing of p.)"""
+        prm = self._edwards_params(prm)
+        ((x, y),), _ = self._points([p])
+        xy2 = self._emit([x, y, self.zero, self.zero], {"q_mul0": 2})
+        xx, yy = self.mul(x, x), self.mul(y, y)
+        dx, ny = self.lc([xx, yy], [prm.a, 1]), self.lc([yy, xx], [1, -prm.a])
+        dy = self.lc([xx, yy], [-prm.a, -1], const=2)
+        return self.div(xy2, dx), self.div(ny, dy)
+
+    def point_neg(self, p):
+        """-(x, y) = (-x, y): one lc gate."""
+        ((x, y),), _ = self._points([p])
+        return self.lc([x], [-1]), y
+
+    def point_select(self, bit, p, q):
+        """p where bit = 1, q where bit = 0: two select gates, 1 level.  The caller makes bit boolean."""
+        ((px, py), (qx, qy)), (bit,) = self._points([p, q], [bit])
+        return self.select(bit, px, qx), self.select(bit, py, qy)
+
+    def enforce_on_curve(self, p, prm=None):
+        """a x^2 + y^2 = 1 + d x^2 y^2: two mul gates and one constraint gate."""
+        prm = self._edwards_params(prm)
+        ((x, y),), _ = self._points([p])
+        xx, yy = self.mul(x, x), self.mul(y, y)
+        self._emit([xx, yy, self.zero, self.zero], {"q_lc0": prm.a, "q_lc1": 1, "q_mul0": -prm.d, "q_c": -1, "q_o": 0}, out=self.zero)
+
+    def enforce_point_equal(self, p, q):
+        """two enforce_equal gates"""
+        ((px, py), (qx, qy)), _ = self._points([p, q])
+        self.enforce_equal(px, qx)
+        self.enforce_equal(py, qy)
+
+    def to_bits_strict(self, x):
+        """ALL bit_length(r) bits of the canonical residue of x, LSB first: the bit gates and the recomposition of to_bits, which at this
+        width holds for x and for x + r alike, and the comparison that excludes the latter — the bits read as an integer are <= r - 1.
+        From the top bit down `run` = [every bit so far that is set in r - 1 is set]: run <- run * bit at a set bit of r - 1 (a mul gate),
+        run * bit = 0 enforced at a clear one.  Per element L + 1 + ceil((L - 4) / 3) + (L - 1) gates for L = bit_length(r) (r - 1 ends in
+        zeros on both fields): 592 on bn254, 594 on bls12_381; the run is a chain of popcount(r - 1) levels."""
+        p = self.field.p
+        L = p.bit_length()
+        x = self._var(x)
+        bits = self._recompose([self.bit(x, k) for k in range(L)], x)
+        c = p - 1
+        lowest_clear = next(i for i in range(L) if not (c >> i) & 1)
+        run = bits[L - 1]
+        for i in range(L - 2, lowest_clear - 1, -1):
+            if (c >> i) & 1:
+                run = self.mul(run, bits[i])
+            else:
+                self._emit([run, bits[i], self.zero, self.zero], {"q_mul0": 1, "q_o": 0}, out=self.zero)
+        return bits
+
+    def _point_or_identity(self, bit, p):
+        """p where bit = 1, (0, 1) where bit = 0: (bit x, 1 + bit (y - 1)), 2 gates"""
+        x, y = p
+        return self.mul(bit, x), self._emit([bit, y, self.zero, self.zero], {"q_mul0": 1, "q_lc0": -1, "q_c": 1})
+
+    def scalar_mul(self, bits, p, prm=None):
+        """[sum 2^i bits[i]] p for p ON E; bits: a list of boolean variables, LSB first, as to_bits and to_bits_strict return them.  Per
+        bit the addend (p_i where the bit is set, else the identity: 2 gates), its addition to the sum (point_add: 9) and p_{i+1} = 2 p_i
+        (point_double: 8); the first bit needs no addition and the last no doubling: 19 nbits - 17 gates per instance.  The doublings do
+        not wait for the sum, so the depth is that of the additions: 4 nbits levels."""
+        prm = self._edwards_params(prm)
+        bits = list(bits)
+        if not bits:
+            raise ValueError("scalar_mul: no bits")
+        (base,), bits = self._points([p], bits)
+        acc = None
+        for i, bit in enumerate(bits):
+            q = self._point_or_identity(bit, base)
+            acc = q if acc is None else self.point_add(acc, q, prm)
+            if i + 1 < len(bits):
+                base = self.point_double(base, prm)
+        return acc
+
+    def fixed_base_mul(self, bits, prm=None):
+        """[sum 2^i bits[i]] G for the generator of prm; bits as in scalar_mul.  The multiples C_i = 2^i G are constants, and adding
+        (C_i where the bit is set, else the identity) = (cx b, 1 + (cy - 1) b) to (x, y) has, with b^2 = b, numerators and denominators of
+        degree two: x + (cy - 1) b x + cx b y,  y + (cy - 1) b y - a cx b x,  1 +- d cx cy b (x y) — 7 gates per bit (two numerators, x y,
+        two denominators, two div) in 3 levels, no select; the first bit is two lc gates: 7 nbits - 5 gates per instance."""
+        prm = self._edwards_params(prm)
+        bits = list(bits)
+        if not bits:
+            raise ValueError("fixed_base_mul: no bits")
+        bits = self._same_length(bits)
+        z, a, d = self.zero, prm.a, prm.d
+        cx, cy = prm.generator
+        x, y = self.lc([bits[0]], [cx]), self.lc([bits[0]], [cy - 1], const=1)
+        for bit in bits[1:]:
+            cx, cy = prm.add_int((cx, cy), (cx, cy))
+            nx = self._emit([bit, x, bit, y], {"q_mul0": cy - 1, "q_mul1": cx, "q_lc1": 1})
+            ny = self._emit([bit, y, bit, x], {"q_mul0": cy - 1, "q_mul1": -a * cx, "q_lc1": 1})
+            xy = self.mul(x, y)
+            dx = self._emit([bit, xy, z, z], {"q_mul0": d * cx * cy, "q_c": 1})
+            dy = self._emit([bit, xy, z, z], {"q_mul0": -d * cx * cy, "q_c": 1})
+            x, y = self.div(nx, dx), self.div(ny, dy)
+        return x, y
+
+    def schnorr_verify(self, pk, message, R, s, prm=None, rescue=None):
+        """The signature (R, s) of edwards.schnorr_sign on `message` under pk:  [s] G = R + [c] pk  with  c = hash3(hash3(R.x, R.y, pk.x),
+        pk.y, message).  s: a variable (decomposed here with to_bits to bit_length(l) bits), or a LIST of that many bit variables, LSB
+        first (made boolean here).  enforce_on_curve(R), the two rescue_hash3, to_bits_strict(c) — c multiplies pk as the integer in
+        [0, r) that the device's kernel takes it for —, fixed_base_mul, scalar_mul, point_add, enforce_point_equal: 7798 gates per
+        signature on bn254, 7827 on bls12_381 with the default parameters (n = 2^13 for one signature).
+        NOT proved: that pk is on E and in the subgroup of order l — pk is public, check it outside with edwards.in_subgroup, as the
+        doublings of scalar_mul assume pk on E; that R lies in that subgroup (the cofactor is 8: R may carry a component of small order,
+        which the equation then forces onto [c] pk — impossible for pk in the subgroup, so R is in it whenever pk is); that s < l (any
+        s < 2^bit_length(l) with the same residue mod l is accepted: edwards.schnorr_verify refuses s >= l)."""
+        prm, rp = self._edwards_params(prm), self._rescue_params(rescue)
+        lbits = prm.order.bit_length()
+        s_is_bits = isinstance(s, (list, tuple))
+        if s_is_bits and len(s) != lbits:
+            raise ValueError(f"s: {len(s)} bits, the order has {lbits}")
+        self._nbits(lbits, self.field.p.bit_length() - 1)
+        (pk, R), rest = self._points([pk, R], [message] + (list(s) if s_is_bits else [s]))
+        message, s = rest[0], rest[1:]
+        self.enforce_on_curve(R, prm)
+        if s_is_bits:
+            s_bits = list(s)
+            for b in s_bits:
+                self.enforce_bool(b)
+        else:
+            s_bits = self.to_bits(s[0], lbits)
+        c = self.rescue_hash3(self.rescue_hash3(R[0], R[1], pk[0], rp), pk[1], message, rp)
+        c_bits = self.to_bits_strict(c)
+        lhs = self.fixed_base_mul(s_bits, prm)
+        rhs = self.point_add(R, self.scalar_mul(c_bits, pk, prm), prm)
+        self.enforce_point_equal(lhs, rhs)
 
     # ------------------------------------------------------------------ constraints
     def enforce_equal(self, a, b):

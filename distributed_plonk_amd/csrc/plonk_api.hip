@@ -93,6 +93,8 @@ struct plonk_ctx {
     unsigned long long* d_bad = nullptr;        // two words for that check's verdict
     Fr* d_rescue = nullptr;                     // Rescue parameters (116 Fr) as last uploaded, and the host bytes they were uploaded from
     std::vector<uint64_t> h_rescue;
+    Fr* d_edwards_table = nullptr;              // window table of the Edwards generator (EDWARDS_TABLE_BYTES), and the parameter words it was built from
+    std::vector<uint64_t> h_edwards;
     uint32_t* d_replay_seg = nullptr;           // segment starts of the solve schedule as last uploaded (plonk_circuit_replay_dev), and their host copy
     size_t replay_seg_cap = 0;                  // words allocated
     std::vector<uint32_t> h_replay_seg;
@@ -221,6 +223,7 @@ extern "C" void plonk_destroy(plonk_ctx* ctx) {
     if (ctx->d_wire) (void)hipFree(ctx->d_wire);
     if (ctx->d_bad) (void)hipFree(ctx->d_bad);
     if (ctx->d_rescue) (void)hipFree(ctx->d_rescue);
+    if (ctx->d_edwards_table) (void)hipFree(ctx->d_edwards_table);
     if (ctx->d_replay_seg) (void)hipFree(ctx->d_replay_seg);
     if (ctx->d_scratch)(void)hipFree(ctx->d_scratch);
     if (ctx->d_scratch2) (void)hipFree(ctx->d_scratch2);
@@ -1430,6 +1433,54 @@ extern "C" int plonk_circuit_scatter_inputs_dev(plonk_ctx* ctx, const void* d_in
     if (rc) return rc;
     return circuit_scatter_inputs_run((const uint32_t*)d_input_vars, num_inputs, (const Fr*)d_inputs, (Fr*)d_witness, num_vars, ctx->d_scratch2, ctx->stream,
                                       "plonk_circuit_scatter_inputs_dev");
+}
+// ---- the embedded Edwards curve (edwards_kernels.hpp).  The parameters travel as kernel arguments; only the generator's window table lives
+// on the device: built on the context's stream when the parameter words differ from those it was built from, so a launch that still reads the
+// old table runs before the rebuild.
+static int edwards_table(plonk_ctx* ctx, const uint64_t* params) {
+    if (ctx->d_edwards_table && ctx->h_edwards.size() == EDWARDS_PARAM_WORDS && !memcmp(ctx->h_edwards.data(), params, EDWARDS_PARAM_WORDS * 8)) return PLONK_OK;
+    if (!ctx->d_edwards_table) HIP_TRY(hipMalloc((void**)&ctx->d_edwards_table, EDWARDS_TABLE_BYTES));
+    ctx->h_edwards.clear();
+    int rc = edwards_table_run(ctx->curve, params, ctx->d_edwards_table, ctx->stream);
+    if (rc) return rc;
+    ctx->h_edwards.assign(params, params + EDWARDS_PARAM_WORDS);
+    return PLONK_OK;
+}
+extern "C" int plonk_edwards_mul_dev(plonk_ctx* ctx, const uint64_t* params, const void* d_scalars, const void* d_points, size_t count, void* d_out) {
+    CHECK_CTX(ctx);
+    if (!params) return plonk_fail(PLONK_ERR_ARG, "plonk_edwards_mul_dev: params is null");
+    if (!d_scalars) return plonk_fail(PLONK_ERR_ARG, "plonk_edwards_mul_dev: d_scalars is null");
+    if (!d_points) return plonk_fail(PLONK_ERR_ARG, "plonk_edwards_mul_dev: d_points is null");
+    if (!d_out) return plonk_fail(PLONK_ERR_ARG, "plonk_edwards_mul_dev: d_out is null");
+    if (count == 0) return PLONK_OK;
+    return edwards_mul_run(ctx->curve, params, (const Fr*)d_scalars, (const Fr*)d_points, count, (Fr*)d_out, ctx->stream, "plonk_edwards_mul_dev");
+}
+extern "C" int plonk_edwards_fixed_mul_dev(plonk_ctx* ctx, const uint64_t* params, const void* d_scalars, size_t count, void* d_out) {
+    CHECK_CTX(ctx);
+    if (!params) return plonk_fail(PLONK_ERR_ARG, "plonk_edwards_fixed_mul_dev: params is null");
+    if (!d_scalars) return plonk_fail(PLONK_ERR_ARG, "plonk_edwards_fixed_mul_dev: d_scalars is null");
+    if (!d_out) return plonk_fail(PLONK_ERR_ARG, "plonk_edwards_fixed_mul_dev: d_out is null");
+    if (count == 0) return PLONK_OK;
+    int rc = edwards_table(ctx, params);
+    if (rc) return rc;
+    return edwards_fixed_mul_run(ctx->curve, params, (const Fr*)d_scalars, count, ctx->d_edwards_table, (Fr*)d_out, ctx->stream, "plonk_edwards_fixed_mul_dev");
+}
+extern "C" int plonk_edwards_add_dev(plonk_ctx* ctx, const uint64_t* params, const void* d_p, const void* d_q, size_t count, void* d_out) {
+    CHECK_CTX(ctx);
+    if (!params) return plonk_fail(PLONK_ERR_ARG, "plonk_edwards_add_dev: params is null");
+    if (!d_p) return plonk_fail(PLONK_ERR_ARG, "plonk_edwards_add_dev: d_p is null");
+    if (!d_q) return plonk_fail(PLONK_ERR_ARG, "plonk_edwards_add_dev: d_q is null");
+    if (!d_out) return plonk_fail(PLONK_ERR_ARG, "plonk_edwards_add_dev: d_out is null");
+    if (count == 0) return PLONK_OK;
+    return edwards_add_run(ctx->curve, params, (const Fr*)d_p, (const Fr*)d_q, count, (Fr*)d_out, ctx->stream, "plonk_edwards_add_dev");
+}
+extern "C" int plonk_edwards_check_dev(plonk_ctx* ctx, const uint64_t* params, const void* d_points, size_t count, void* d_flags) {
+    CHECK_CTX(ctx);
+    if (!params) return plonk_fail(PLONK_ERR_ARG, "plonk_edwards_check_dev: params is null");
+    if (!d_points) return plonk_fail(PLONK_ERR_ARG, "plonk_edwards_check_dev: d_points is null");
+    if (!d_flags) return plonk_fail(PLONK_ERR_ARG, "plonk_edwards_check_dev: d_flags is null");
+    if (count == 0) return PLONK_OK;
+    return edwards_check_run(ctx->curve, params, (const Fr*)d_points, count, (uint32_t*)d_flags, ctx->stream, "plonk_edwards_check_dev");
 }
 extern "C" int plonk_debug_field_op(plonk_ctx* ctx, int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
     CHECK_CTX(ctx);

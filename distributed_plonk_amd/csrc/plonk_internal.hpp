@@ -266,6 +266,15 @@ int rescue_acc_paths_run(int curve, const Fr* d_nodes, uint64_t count, unsigned 
                          hipStream_t stream, const char* who);
 int circuit_scatter_inputs_run(const uint32_t* d_input_vars, size_t num_inputs, const Fr* d_inputs, Fr* d_witness, size_t num_vars, void* scratch, hipStream_t stream,
                                const char* who);
+// The embedded twisted Edwards curve over Fr (edwards_kernels.hpp, built in synth.hip).  params: HOST, 20 u64 = a, d, G.x, G.y Montgomery then the
+// subgroup order l as 4 plain limbs; points: [count][2] Fr affine; table: EDWARDS_TABLE_BYTES on the device, written by edwards_table_run from
+// the G of `params` and read by edwards_fixed_mul_run; flags: u32 [count].  count > 0.  Enqueued only.
+constexpr size_t EDWARDS_PARAM_WORDS = 20, EDWARDS_TABLE_BYTES = 64 * 16 * 64;
+int edwards_table_run(int curve, const uint64_t* params, Fr* d_table, hipStream_t stream);
+int edwards_mul_run(int curve, const uint64_t* params, const Fr* d_scalars, const Fr* d_points, size_t count, Fr* d_out, hipStream_t stream, const char* who);
+int edwards_fixed_mul_run(int curve, const uint64_t* params, const Fr* d_scalars, size_t count, const Fr* d_table, Fr* d_out, hipStream_t stream, const char* who);
+int edwards_add_run(int curve, const uint64_t* params, const Fr* d_p, const Fr* d_q, size_t count, Fr* d_out, hipStream_t stream, const char* who);
+int edwards_check_run(int curve, const uint64_t* params, const Fr* d_points, size_t count, uint32_t* d_flags, hipStream_t stream, const char* who);
 
 // ----------------------------------------------------------------------------------------------- O(n) prover steps (poly_ops.hip, quotient.hip)
 int quotient_evals_run(NttTables& T, const plonk_quotient_inputs* in, size_t n, size_t m, const uint64_t* alpha, const uint64_t* beta,

@@ -364,6 +364,8 @@ int synth_circuit_dev(int curve, uint64_t seed, size_t n, size_t num_inputs, con
 #include "rescue_kernels.hpp"
 // the ternary accumulator over it, its membership paths, and the scatter that starts a solve from inputs on the device
 #include "rescue_acc_kernels.hpp"
+// the embedded twisted Edwards curve over Fr: scalar multiplication, addition and the curve / subgroup check, on the same power for the inversion
+#include "edwards_kernels.hpp"
 
 // ---------------------------------------------------------------------------------------------- batched proof verification
 // the per-proof work of jf-plonk's verify / batch_verify up to the pairing: kernels and launcher in their own header

@@ -476,6 +476,28 @@ class PlonkWorker:
         sib2, is_left, is_right (plonk_rescue_acc_paths_dev).  Synchronises."""
         check(self.lib.plonk_rescue_acc_paths_dev(self.ctx, d_nodes or None, count, height, d_elems or None, d_uids or None, m, d_inputs_out or None))
 
+    # ------------------------------------------------------------------ the embedded Edwards curve (distributed_plonk_amd/edwards.py)
+    def edwards_mul_dev(self, params: Optional[np.ndarray], d_scalars: int, d_points: int, count: int, d_out: int):
+        """d_out[i] = [scalars[i]] points[i] (plonk_edwards_mul_dev); params: 20 u64 = a, d, G.x, G.y Montgomery, then l plain; scalars [count] Fr,
+        points [count][2] Fr.  Enqueued on the context's stream, not synchronised."""
+        p = None if params is None else _u64(params)
+        check(self.lib.plonk_edwards_mul_dev(self.ctx, _ptr(p), d_scalars or None, d_points or None, count, d_out or None))
+
+    def edwards_fixed_mul_dev(self, params: Optional[np.ndarray], d_scalars: int, count: int, d_out: int):
+        """d_out[i] = [scalars[i]] G from the context's window table of G (plonk_edwards_fixed_mul_dev).  Enqueued, not synchronised."""
+        p = None if params is None else _u64(params)
+        check(self.lib.plonk_edwards_fixed_mul_dev(self.ctx, _ptr(p), d_scalars or None, count, d_out or None))
+
+    def edwards_add_dev(self, params: Optional[np.ndarray], d_p: int, d_q: int, count: int, d_out: int):
+        """d_out[i] = p[i] + q[i] (plonk_edwards_add_dev).  Enqueued, not synchronised."""
+        p = None if params is None else _u64(params)
+        check(self.lib.plonk_edwards_add_dev(self.ctx, _ptr(p), d_p or None, d_q or None, count, d_out or None))
+
+    def edwards_check_dev(self, params: Optional[np.ndarray], d_points: int, count: int, d_flags: int):
+        """d_flags[i] (u32): bit 0 on the curve, bit 1 in the subgroup of order l (plonk_edwards_check_dev).  Enqueued, not synchronised."""
+        p = None if params is None else _u64(params)
+        check(self.lib.plonk_edwards_check_dev(self.ctx, _ptr(p), d_points or None, count, d_flags or None))
+
     def circuit_scatter_inputs_dev(self, d_input_vars: int, num_inputs: int, d_inputs: int, d_witness: int, num_vars: int):
         """witness[input_vars[k]] = inputs[k] on the device (plonk_circuit_scatter_inputs_dev); d_input_vars: u32.  Synchronises."""
         check(self.lib.plonk_circuit_scatter_inputs_dev(self.ctx, d_input_vars or None, num_inputs, d_inputs or None, d_witness or None, num_vars))

@@ -442,6 +442,25 @@ int plonk_rescue_acc_paths_dev(plonk_ctx* ctx, const void* d_nodes, size_t count
  * NULL pointer, num_vars outside 1 .. 2^32 - 2, and naming the first k with input_vars[k] >= num_vars (checked on the device; nothing is
  * written for such a k).  Synchronises. */
 int plonk_circuit_scatter_inputs_dev(plonk_ctx* ctx, const void* d_input_vars, size_t num_inputs, const void* d_inputs, void* d_witness, size_t num_vars);
+/* The embedded twisted Edwards curve E: a x^2 + y^2 = 1 + d x^2 y^2 over the context's Fr (Baby Jubjub on BN254, Jubjub on BLS12-381;
+ * distributed_plonk_amd/edwards.py holds the parameters), the group builder.py's point gadgets prove.  a is a square and d a non-square, so the
+ * addition law is complete: doubling, inverses, the identity (0, 1) and the points of small order need no special case.  params: HOST, 20 u64 =
+ * a, d, G.x, G.y as Fr Montgomery, then the order l of G as 4 plain limbs; they travel as kernel arguments.  Points: [count][2] Fr Montgomery,
+ * affine (x, y).  Scalars: [count] Fr Montgomery; a scalar stands for its canonical residue k in [0, r), so a hash output multiplies a point
+ * directly.  One lane per element, extended coordinates in registers, one inversion (~335 products) per result.  All four are ordered on the
+ * context's stream and return once the work is enqueued; count = 0 is a no-op; PLONK_ERR_ARG naming the argument for a NULL pointer, and for a
+ * count beyond one launch.
+ * mul: d_out[i] = [k_i] d_points[i], bit_length(r) doublings and as many additions, each computed and then selected (~5.2 k products, no
+ * divergence).  d_out may be d_points.  The points must lie on E (plonk_edwards_check_dev); for others the result is unspecified. */
+int plonk_edwards_mul_dev(plonk_ctx* ctx, const uint64_t* params, const void* d_scalars, const void* d_points, size_t count, void* d_out);
+/* d_out[i] = [k_i] G from a table of [j 16^w] G, j < 16, w < 64 (64 KB, affine) in a context-owned device buffer: built on the device when the
+ * 20 words of params differ from those of the last call, then 64 gathered additions per lane (~1.0 k products). */
+int plonk_edwards_fixed_mul_dev(plonk_ctx* ctx, const uint64_t* params, const void* d_scalars, size_t count, void* d_out);
+/* d_out[i] = d_p[i] + d_q[i] by the unified law (also the doubling: d_p = d_q), affine and exact.  d_out may be d_p or d_q. */
+int plonk_edwards_add_dev(plonk_ctx* ctx, const uint64_t* params, const void* d_p, const void* d_q, size_t count, void* d_out);
+/* d_flags: u32 [count].  Bit 0: the point satisfies the curve equation.  Bit 1: it does and [l] point = (0, 1), i.e. it lies in the subgroup of
+ * prime order l (l < r: one run of mul's loop over bit_length(l) bits, without the inversion). */
+int plonk_edwards_check_dev(plonk_ctx* ctx, const uint64_t* params, const void* d_points, size_t count, void* d_flags);
 /* G2 and the pairing, host-only (no context, no GPU), for the verifier's last step e(A, [tau]_2) * e(-B, [1]_2) == 1 (jf-plonk's verify).
  * G2 points lie on the sextic twist (BN254: y^2 = x^3 + 3/(9+u), BLS12-381: y^2 = x^3 + 4(1+u); Fq2 = Fq[u]/(u^2+1)) and are encoded as
  * x.c0 || x.c1 || y.c0 || y.c1 Montgomery limbs (4Q u64), all zero = infinity; G1 points as x || y (2Q u64), (0, 0) = infinity.  Coordinates
