@@ -1,10 +1,11 @@
 """The solve schedule and its replay (plonk_circuit_schedule_dev / plonk_circuit_replay_dev behind BuiltCircuit.schedule, solve_many_dev and
-setup): the recorded order against a restatement from tests/hint_ref.py (the level of def_gate[v] is lvl[v], the class comes from the
-opcode, ties break by gate), replayed witnesses limb for limb against solve_dev for every fuse width, the shapes at which each launch form
+setup): the recorded order against a restatement from tests/hint_ref.py (tests/replay_ref.py: the level of def_gate[v] is lvl[v], the class
+comes from the opcode, ties break by gate), replayed witnesses limb for limb against solve_dev for every fuse width, the shapes at which each launch form
 can go wrong (a segment wider than a workgroup times K; a fused run of more than 64 levels of a few gates), device inputs, and one
 accumulator's memberships set up once and proved per witness.
 
-tests/test_hostemu_solve_replay.py runs a selection of this file on the CPU."""
+tests/test_hostemu_solve_replay.py runs a selection of this file on the CPU; tools/fuzz_abi.py (`--only replay`) replays random layered circuits
+at the launch plan's boundaries against the reference solver."""
 import random
 
 import numpy as np
@@ -18,7 +19,8 @@ from distributed_plonk_amd import verifier as VF
 from distributed_plonk_amd.membership import membership_circuit
 from distributed_plonk_amd.prover import Prover
 from distributed_plonk_amd.worker import REPLAY_FUSE_DEFAULT
-from tests.hint_ref import GIVEN, HintRefSolver
+from tests.hint_ref import HintRefSolver
+from tests.replay_ref import ref_schedule
 
 pytestmark = pytest.mark.gpu
 
@@ -117,19 +119,6 @@ def case(curve: str, name: str, K: int):
 def limbs3(ref, rows) -> np.ndarray:
     """K rows of residues -> (K, len, 4) Montgomery limbs"""
     return np.stack([ref.limbs(r).reshape(-1, 4) for r in rows]) if rows[0] else np.zeros((len(rows), 0, 4), dtype=np.uint64)
-
-
-def class_of(opcode: int) -> int:
-    return 1 if opcode in (BD.HINT_INV, BD.HINT_DIV) else 2 if opcode == BD.HINT_ROOT5 else 0
-
-
-def ref_schedule(built, ref):
-    """-> (order, seg, levels, evaluations) from the reference's levels: gates sorted by (level, class, gate)"""
-    keyed = sorted((3 * ref.lvl[v] + class_of(ref.opcode(int(g))), int(g)) for v, g in enumerate(built.def_gate) if g != GIVEN)
-    levels = ref.depth()
-    keys = np.array([k for k, _ in keyed], dtype=np.int64)
-    seg = np.searchsorted(keys, np.arange(3 * levels + 1), side="left").astype(np.uint32)
-    return np.array([g for _, g in keyed], dtype=np.uint32), seg, levels, len(keyed)
 
 
 def solved_one_by_one(w, built, ref, ins, pubs):

@@ -369,6 +369,17 @@ def test_differential_fuzz_slice_of_the_circuit_operations(emu_env):
     assert r.returncode == 0 and "fuzz ok: 20 operations" in r.stdout, (r.stdout + r.stderr)[-2000:]
 
 
+def test_differential_fuzz_slice_of_the_curve_operations(emu_env):
+    """The fuzzer's `curve` group — the Edwards kernels alone and enqueued back to back under three parameter sets, Schnorr signatures with one
+    drawn defect, random chains of the builder's point gadgets, the recorded solve schedule and its replay for K witnesses — with plonk_trim,
+    transforms, MSMs and rounds under new commit keys between them, on one long-lived (emulated) context, against tests/edwards_ref.py,
+    hint_ref.py, replay_ref.py and rescue_ref.py.  The seeds of tests/test_gpu_fuzz_slice.py pin the draw counts and branches; this one runs
+    where no GPU exists."""
+    r = subprocess.run([sys.executable, "tools/fuzz_abi.py", "--seconds", "800", "--max-ops", "12", "--seed", "9", "--max-log", "8", "--ops", "curve,trim,ntt,msm,round1"],
+                       cwd=ROOT, env=emu_env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "fuzz ok: 12 operations" in r.stdout, (r.stdout + r.stderr)[-2000:]
+
+
 def test_second_device_of_one_process_raises_its_own_lds_limits(emu_env):
     """The emulation enforces the runtime's dynamic-LDS rule per (device, kernel): a launch above 64 KiB aborts unless
     hipFuncSetAttribute(MaxDynamicSharedMemorySize) was called for that kernel ON THAT DEVICE.  A second worker on another device of the

@@ -6,22 +6,28 @@ forced options in between, every result compared bit-for-bit with its reference.
 
     python tools/fuzz_abi.py --seconds 600 [--seed 1] [--curve bn254|bls12_381|both] [--max-log 13] [--ops NAME[,NAME...]] [--only NAME] [--trace]
 
-Twenty-five operations in two groups.  `core` (nineteen, against oracle/oracle.py): transforms, MSMs and batched commitments, polynomial
+Twenty-nine operations in three groups.  `core` (nineteen, against oracle/oracle.py): transforms, MSMs and batched commitments, polynomial
 operations, the grand product, quotient evaluations, distributed transforms, refused SRSs, trim, whole proofs handed to the verifier.
 `circuit` (six): circuit_preprocess (plonk_circuit_permutation_dev / _witness_dev / _check_dev against a stable argsort and a big-integer gate
 evaluation), solve (the level-by-level witness solver, plain or hinted, against tests/solve_ref.py / hint_ref.py, with planted cycles,
 refused definitions and the witness carried into preprocessing), rescue (permutation and Merkle kernels against tests/rescue_ref.py,
 default and injected parameters by coin), accumulator (the ternary tree and its path gather against tests/accumulator_ref.py),
 verify_batch (plonk_verify_batch_dev on batches of honest and mutated proofs against oracle/verifier_ref.py) and membership (accumulator,
-gather, solve, preprocess, prove, verify, then a spoiled instance).  --ops takes operation and group names and draws from that list
-(default: all; `--ops core` is draw for draw the fuzzer as it was before the circuit group); --only runs one operation.  Whatever --max-log
-says, a circuit operation stays below 2^12 gates and about 200 reference Rescue permutations, so that no draw waits long for its reference.
+gather, solve, preprocess, prove, verify, then a spoiled instance).  `curve` (four, against tests/edwards_ref.py, hint_ref.py and replay_ref.py):
+edwards (the mul / fixed_mul / add / check kernels alone or enqueued back to back, on edge and fresh operands, under the default parameters,
+another generator or an isomorphic scaled curve, with the output over an input and the generator's table rebuilt between launches), schnorr
+(keygen, sign and verify of up to six signatures with one drawn defect), edwards_gadgets (a random chain of the builder's point gadgets solved,
+preprocessed and spoiled) and replay (the recorded solve schedule and K replayed witnesses of a layered circuit under two fuse widths, with
+planted cycles).  --ops takes operation and group names and draws from that list (default: all; `--ops core` is draw for draw the fuzzer as
+it was before the circuit group); --only runs one operation.  Whatever --max-log says, a circuit operation stays below 2^12 gates and about
+200 reference Rescue permutations, and a curve operation below 2^10 points and 24 fresh reference scalar multiplications, so that no draw
+waits long for its reference.  The final line counts the operations drawn (`per op`) and the branches the curve operations took (`branches`).
 
 It drives whatever library `distributed_plonk_amd._ffi` loads: libplonk_hip.so on an MI355X, or — in the GPU-less build container —
 the host emulation (tests/hostemu; PLONK_HIP_LIB=tests/hostemu/_build/plain/libplonk_hostemu.so PLONK_ALLOW_HOSTEMU=1), where it
 is also worth running against the AddressSanitizer build.  The first mismatch prints the operation and its parameters (enough to
 replay it with --seed and the same --ops / --only) and exits 1; a HIP error or any unexpected exception ends the run.
-tests/test_hostemu.py runs two short fixed-seed slices of it in the CPU suite, tests/test_gpu_fuzz_slice.py five on the device.
+tests/test_hostemu.py runs three short fixed-seed slices of it in the CPU suite, tests/test_gpu_fuzz_slice.py nine on the device.
 """
 import argparse
 import os
@@ -51,6 +57,9 @@ class Fuzz:
         self.proved = None                            # op_verify_batch's proved instance
         self.membership_built = {}                    # op_membership's circuits under the default parameters, by (height, m)
         self.key_epoch = 0                            # counts the installs of a commit key on self.w, whichever operation made them
+        self.branches = {}                            # which branches the curve operations took (hit)
+        self._ed = None                               # ed_pool's operands and reference caches
+        self.ed_fresh = 0                             # reference scalar multiplications computed by the current operation
         for name in ("init", "init_dev"):
             setattr(self.w, name, self._counting(getattr(self.w, name)))
 
@@ -767,13 +776,38 @@ class Fuzz:
                 b.free()
         return bool(ok), info
 
+    @staticmethod
+    def rebuilt(built, wire_vars=None, selector_evals=None, def_gate=None):
+        """a copy of `built` with some of its arrays replaced"""
+        from distributed_plonk_amd import builder as BD
+        pick = lambda new, old: old.copy() if new is None else new
+        return BD.BuiltCircuit(built.curve, pick(wire_vars, built.wire_vars), pick(selector_evals, built.selector_evals), built.num_vars,
+                               pick(def_gate, built.def_gate), built.input_vars, built.public_vars, built.zero_var, built.num_gates_unpadded,
+                               hint_op=built.hint_op.copy())
+
+    def planted_cycle(self, built, ref, defined):
+        """`built` with a dependency cycle x -> y -> x (or x -> x), x < y, among the `defined` variables -> (circuit, x, y), or None where no
+        defined variable has a live wire to bend"""
+        rs = self.rs
+        cands = [v for v in defined[rs.permutation(defined.size)[:64]] if ref.live_wires(int(built.def_gate[v]))]
+        if not cands:
+            return None
+        x = int(cands[0])
+        gx = int(built.def_gate[x])
+        users = [int(built.wire_vars[4, g]) for g in range(built.n)
+                 if int(built.def_gate[int(built.wire_vars[4, g])]) == g and int(built.wire_vars[4, g]) > x
+                 and any(int(built.wire_vars[i, g]) == x for i in ref.live_wires(g))]
+        y = users[int(rs.randint(0, len(users)))] if users else x
+        wv = built.wire_vars.copy()
+        wv[ref.live_wires(gx)[0], gx] = y
+        return self.rebuilt(built, wire_vars=wv), x, y
+
     def op_solve(self):
         """plonk_circuit_solve_dev / plonk_circuit_solve_hints_dev on a random layered circuit whose number of rounds and width are drawn
         here: the witness bit for bit and the level / evaluation counters against RefSolver / HintRefSolver; now and then a planted
         dependency cycle (the smallest variable on it is reported), a definition the entry must refuse (and a good solve right after), and
         the solved witness carried into preprocess_dev and plonk_circuit_check_dev, whose verdict must be the reference's: satisfied, or its
         first unsatisfied gate (none without a planted constraint, unless a hinted inverse or quotient met a zero)."""
-        from distributed_plonk_amd import builder as BD
         from distributed_plonk_amd import circuit as CI
         from distributed_plonk_amd._ffi import PlonkError
         from tests.circuit_cases import layered_circuit, ref_perm_idx
@@ -791,12 +825,7 @@ class Fuzz:
         Ref = HintRefSolver if built.has_hints else RefSolver
         info = dict(hints=hints, width=width, depth=depth, cseed=cseed, n=built.n, planted=planted)
 
-        def rebuilt(wire_vars=None, selector_evals=None, def_gate=None):
-            pick = lambda new, old: old.copy() if new is None else new
-            return BD.BuiltCircuit(built.curve, pick(wire_vars, built.wire_vars), pick(selector_evals, built.selector_evals), built.num_vars,
-                                   pick(def_gate, built.def_gate), built.input_vars, built.public_vars, built.zero_var, built.num_gates_unpadded,
-                                   hint_op=built.hint_op.copy())
-
+        rebuilt = lambda **changed: self.rebuilt(built, **changed)
         ref = Ref(built, inputs, publics)
         in_limbs, pub_limbs = ref.limbs(inputs), ref.limbs(publics)
         defined = np.flatnonzero(built.def_gate != GIVEN)
@@ -805,17 +834,9 @@ class Fuzz:
         pick_var = rs.rand()
         try:
             if pick_var < 0.125 and defined.size:                     # a dependency cycle x -> y -> x (or x -> x), x < y
-                cands = [v for v in defined[rs.permutation(defined.size)[:64]] if ref.live_wires(int(built.def_gate[v]))]
-                if cands:
-                    x = int(cands[0])
-                    gx = int(built.def_gate[x])
-                    users = [int(built.wire_vars[4, g]) for g in range(built.n)
-                             if int(built.def_gate[int(built.wire_vars[4, g])]) == g and int(built.wire_vars[4, g]) > x
-                             and any(int(built.wire_vars[i, g]) == x for i in ref.live_wires(g))]
-                    y = users[int(rs.randint(0, len(users)))] if users else x
-                    wv = built.wire_vars.copy()
-                    wv[ref.live_wires(gx)[0], gx] = y
-                    cyc = rebuilt(wire_vars=wv)
+                planted_cycle = self.planted_cycle(built, ref, defined)
+                if planted_cycle:
+                    cyc, x, y = planted_cycle
                     info.update(what="cycle", x=x, y=y)
                     try:
                         cyc.solve_dev(self.w, in_limbs, pub_limbs).close()
@@ -1264,11 +1285,537 @@ class Fuzz:
                 built.close()
         return bool(ok), info
 
+    # ---------------------------------------------------------------- the embedded Edwards curve, signatures, point gadgets, schedule replay
+    # References: tests/edwards_ref.py, hint_ref.py, solve_ref.py, rescue_ref.py — pure Python.  One reference scalar multiplication or subgroup
+    # test costs about 17 ms; an operation computes at most ED_BUDGET fresh ones and lets the lanes of a launch repeat their operands.
+    ED_BUDGET = 24
+    ED_COUNTS = (1, 2, 63, 64, 65, 255, 256, 257, 511, 513)
+
+    def hit(self, name, by=1):
+        """count a branch that an operation took (printed with the final line)"""
+        self.branches[name] = self.branches.get(name, 0) + by
+
+    def big(self, modulus):
+        """a uniform residue from the operation stream"""
+        return int.from_bytes(self.rs.bytes(40), "little") % modulus
+
+    def pts_limbs(self, points):
+        return self.limbs([v for P in points for v in P]).reshape(-1, 2, 4)
+
+    def pts_ints(self, limbs):
+        flat = self.ints(limbs)
+        return [(flat[2 * i], flat[2 * i + 1]) for i in range(len(flat) // 2)]
+
+    def ed_pool(self):
+        """The operands of the default curve, once per Fuzz object: the edge scalars and points, the points off the curve, and the caches of
+        the reference's results on the default curve — mul[(k, P)] = [k] P and flags[P] = ON_CURVE | IN_SUBGROUP — filled for the edge scalars
+        with G and for the edge points here, lazily (and counted against the operation's budget) for everything else."""
+        if self._ed is None:
+            import random
+            from tests import edwards_ref as E
+            curve = self.curve
+            r, c = E.MODULI[curve], E.PARAMS[curve]
+            l, G = c["l"], c["G"]
+            rnd = random.Random("fuzz edwards " + curve)
+            seams = [1 << k for k in (3, 4, 31, 32, 63, 64, 127, 128, 247, 248, 251, 252, 253, 254) if 1 << k < r]
+            scalars = [0, 1, 2, l - 1, l, l + 1, r - 1] + seams
+            small = E.small_order_points(curve)
+            sub = [E.mul(curve, rnd.randrange(1, l), G) for _ in range(2)]
+            non = []
+            while len(non) < 2:
+                P = E.random_point(curve, rnd)
+                if not E.in_subgroup(curve, P):
+                    non.append(P)
+            points = [E.IDENTITY, small[2], small[4], small[8], G, E.neg(curve, G)] + sub + non
+            off = [(G[0], (G[1] + 1) % r), (0, 0), (1, 1), (r - 1, r - 1), (G[1], G[0])]
+            assert not any(E.on_curve(curve, P) for P in off)
+            self._ed = dict(scalars=scalars, points=points, off=off, small=small, mul={(k, G): E.mul(curve, k, G) for k in scalars},
+                            flags={P: 1 | (2 if E.in_subgroup(curve, P) else 0) for P in points})
+            self._ed["flags"].update({P: 0 for P in off})
+        return self._ed
+
+    def ed_mul(self, k, P, prm=None):
+        """[k] P by the reference: cached on the default curve, evaluated (and counted) afresh under an injected parameter set"""
+        from tests import edwards_ref as E
+        if prm is None:
+            cache = self.ed_pool()["mul"]
+            if (k, P) not in cache:
+                self.ed_fresh += 1
+                cache[(k, P)] = E.mul(self.curve, k, P)
+            return cache[(k, P)]
+        self.ed_fresh += 1
+        return E.mul(self.curve, k, P, prm)
+
+    def ed_flags(self, P, prm=None):
+        from tests import edwards_ref as E
+        if prm is None:
+            cache = self.ed_pool()["flags"]
+            if P not in cache:
+                self.ed_fresh += 1
+                cache[P] = (1 | (2 if E.in_subgroup(self.curve, P) else 0)) if E.on_curve(self.curve, P) else 0
+            return cache[P]
+        if not E.on_curve(self.curve, P, prm):
+            return 0
+        self.ed_fresh += 1
+        return 1 | (2 if E.in_subgroup(self.curve, P, prm) else 0)
+
+    def ed_param_set(self, exclude=None):
+        """One of three parameter sets of the same group: "default"; "generator", [t] G on the default curve; "scaled", the isomorphic curve
+        (a u^2, d u^2) with the generator (G.x / u, G.y), whose points are (x / u, y).  -> dict(name, prm: EdwardsParams, ref: what
+        tests/edwards_ref.py takes as prm= (None for the default), to_set: default-curve point -> this set's point, t: the generator is [t] G)"""
+        from distributed_plonk_amd import edwards as ED
+        from tests import edwards_ref as E
+        rs, curve = self.rs, self.curve
+        r, c = E.MODULI[curve], E.PARAMS[curve]
+        names = [x for x in ("default", "generator", "scaled") if x != exclude]
+        name = names[int(rs.randint(0, len(names)))]
+        if name == "default":
+            return dict(name=name, prm=ED.EdwardsParams.default(curve), ref=None, to_set=lambda P: P, t=1)
+        if name == "generator":
+            t = 2 + self.big(c["l"] - 2)
+            G2 = E.mul(curve, t, c["G"])
+            ref = dict(c, G=G2)
+            return dict(name=name, prm=ED.EdwardsParams(curve, c["a"], c["d"], G2, c["l"], 8), ref=ref, to_set=lambda P: P, t=t)
+        u = 1 + self.big(r - 1)
+        ui = pow(u, -1, r)
+        to_set = lambda P: (P[0] * ui % r, P[1])
+        ref = dict(a=c["a"] * u * u % r, d=c["d"] * u * u % r, cofactor=8, l=c["l"], G=to_set(c["G"]))
+        return dict(name=name, prm=ED.EdwardsParams(curve, ref["a"], ref["d"], ref["G"], ref["l"], 8), ref=ref, to_set=to_set, t=1)
+
+    def ed_lanes(self, count, distinct):
+        """`count` indices into `distinct` operands: each once in order (as far as count goes), then shuffled repeats"""
+        idx = [i % distinct for i in range(count)]
+        tail = idx[distinct:]
+        idx[distinct:] = [tail[int(i)] for i in self.rs.permutation(len(tail))]
+        return idx
+
+    def ed_element(self, kernel, pset, count, budget):
+        """The operands and expected results of one launch: dict(kernel, set, arrays (host inputs, in the entry point's order), want).  Every
+        expected value is computed twice — by the reference under the set's own parameters, and on the default curve carried over by the
+        isomorphism — and the two must agree (-> None otherwise: the reference itself is in doubt)."""
+        import random
+        from tests import edwards_ref as E
+        rs, curve, pool = self.rs, self.curve, self.ed_pool()
+        r, c = E.MODULI[curve], E.PARAMS[curve]
+        l, G = c["l"], c["G"]
+        ref, to_set = pset["ref"], pset["to_set"]
+        rnd = random.Random(self.seed())
+        start = self.ed_fresh
+        spent = lambda: self.ed_fresh - start
+        shuffled = lambda xs: [xs[int(i)] for i in rs.permutation(len(xs))]
+        ops, want = [], []
+        if kernel == "mul":
+            # the pairs of the fixed tests first in a random order, then fresh ones; points of E only (the kernel's contract)
+            cands = shuffled([(k, pool["points"][6]) for k in pool["scalars"]] + [(pool["scalars"][6], P) for P in pool["points"]]
+                             + [(k, pool["points"][8]) for k in pool["scalars"][:7]])
+            cands = cands[:int(rs.randint(0, 12))] + [(self.big(r), E.random_point(curve, rnd)) for _ in range(self.ED_BUDGET)]
+            for k, P in cands:
+                if ops and spent() + 2 > budget:
+                    break
+                direct = self.ed_mul(k, to_set(P), ref) if ref else self.ed_mul(k, P)
+                if direct != to_set(self.ed_mul(k, P)):
+                    return None
+                ops.append((k, to_set(P)))
+                want.append(direct)
+            idx = self.ed_lanes(count, len(ops))
+            arrays = [self.limbs([ops[i][0] for i in idx]), self.pts_limbs([ops[i][1] for i in idx])]
+        elif kernel == "fixed_mul":
+            cands = shuffled(pool["scalars"])[:int(rs.randint(0, 12))] + [self.big(r) for _ in range(self.ED_BUDGET)]
+            for k in cands:
+                if ops and spent() + 2 > budget:
+                    break
+                direct = self.ed_mul(k, ref["G"], ref) if ref else self.ed_mul(k, G)
+                if direct != to_set(self.ed_mul(k * pset["t"] % l if pset["t"] != 1 else k, G)):
+                    return None
+                ops.append(k)
+                want.append(direct)
+            idx = self.ed_lanes(count, len(ops))
+            arrays = [self.limbs([ops[i] for i in idx])]
+        elif kernel == "add":
+            # the complete law costs the reference two inversions: every pair of the pool's points and a few fresh ones
+            pts = pool["points"] + [E.random_point(curve, rnd) for _ in range(2)]
+            for i in rs.permutation(len(pts) ** 2)[:64]:
+                P, Q = pts[int(i) // len(pts)], pts[int(i) % len(pts)]
+                direct = E.add(curve, to_set(P), to_set(Q), ref)
+                if direct != to_set(E.add(curve, P, Q)):
+                    return None
+                ops.append((to_set(P), to_set(Q)))
+                want.append(direct)
+            idx = self.ed_lanes(count, len(ops))
+            arrays = [self.pts_limbs([ops[i][0] for i in idx]), self.pts_limbs([ops[i][1] for i in idx])]
+        else:
+            cands = shuffled(pool["points"] + pool["off"])[:int(rs.randint(4, 16))]
+            cands += [(self.big(r), self.big(r)) for _ in range(2)] + [E.random_point(curve, rnd) for _ in range(self.ED_BUDGET)]
+            for P in cands:
+                if ops and spent() + 2 > budget:
+                    break
+                direct = self.ed_flags(to_set(P), ref) if ref else self.ed_flags(P)
+                if direct != self.ed_flags(P):
+                    return None
+                ops.append(to_set(P))
+                want.append(direct)
+            idx = self.ed_lanes(count, len(ops))
+            arrays = [self.pts_limbs([ops[i] for i in idx])]
+        return dict(kernel=kernel, set=pset, arrays=arrays, want=[want[i] for i in idx], distinct=len(ops))
+
+    def op_edwards(self):
+        """plonk_edwards_mul_dev / _fixed_mul_dev / _add_dev / _check_dev: one launch, or two or three enqueued back to back and read back only
+        at the end; counts around the workgroup size; the edge scalars and points of tests/test_gpu_edwards.py beside fresh ones; one of three
+        parameter sets (ed_param_set); the output over an input by coin; and the generator's table rebuilt between fixed_mul launches under
+        sets A, B, A without a host synchronisation.  Every lane against tests/edwards_ref.py."""
+        from distributed_plonk_amd import edwards as ED
+        rs = self.rs
+        cap = 1 << min(self.max_log, 10)
+        kernels = ["mul", "fixed_mul", "add", "check"]
+        chain = [kernels[int(rs.randint(0, 4))] for _ in range(1 if rs.rand() < 0.4 else int(rs.randint(2, 4)))]
+        if len(chain) > 1 and rs.rand() < 0.3:
+            chain[int(rs.randint(0, len(chain)))] = "fixed_mul"
+            chain[int(rs.randint(0, len(chain)))] = "fixed_mul"
+        set_a = self.ed_param_set()
+        sets = [set_a] * len(chain)
+        fixed = [i for i, k in enumerate(chain) if k == "fixed_mul"]
+        table = len(fixed) >= 2
+        if table:                                                     # A, B, A: the second under another set, a third under the first again
+            sets[fixed[1]] = self.ed_param_set(exclude=set_a["name"])
+            if len(fixed) == 2:
+                chain.append("fixed_mul")
+                sets.append(set_a)
+        self.ed_fresh = 0
+        info = dict(chain=chain, sets=[x["name"] for x in sets], counts=[], alias=[])
+        elements = []
+        for kernel, pset in zip(chain, sets):
+            count = int(rs.choice([x for x in self.ED_COUNTS if x <= cap])) if rs.rand() < 0.6 else int(rs.randint(1, min(600, cap) + 1))
+            el = self.ed_element(kernel, pset, count, max(2, self.ED_BUDGET // len(chain)))
+            if el is None:
+                info.update(what=f"the reference disagrees with itself under the {pset['name']} set ({kernel})")
+                return False, info
+            el["count"] = count
+            el["alias"] = str(rs.choice(["none", "out=points"])) if kernel == "mul" else str(rs.choice(["none", "out=p", "out=q"])) if kernel == "add" else "none"
+            info["counts"].append(count)
+            info["alias"].append(el["alias"])
+            elements.append(el)
+        info["fresh_references"] = self.ed_fresh
+        bufs = []
+        try:
+            for el in elements:                                       # every upload first: an upload waits for the stream
+                el["in"] = [self.up(a) for a in el["arrays"]]
+                bufs += el["in"]
+                if el["alias"] == "none":
+                    el["out"] = self.w.alloc(el["count"] * (4 if el["kernel"] == "check" else 64))
+                    bufs.append(el["out"])
+                else:
+                    el["out"] = el["in"][1 if el["alias"] in ("out=points", "out=q") else 0]
+            for el in elements:                                       # enqueued back to back
+                ptrs, prm, n, out = [b.ptr for b in el["in"]], el["set"]["prm"], el["count"], el["out"].ptr
+                if el["kernel"] == "mul":
+                    ED.mul_dev(self.w, prm, ptrs[0], ptrs[1], n, out)
+                elif el["kernel"] == "fixed_mul":
+                    ED.fixed_mul_dev(self.w, prm, ptrs[0], n, out)
+                elif el["kernel"] == "add":
+                    ED.add_dev(self.w, prm, ptrs[0], ptrs[1], n, out)
+                else:
+                    ED.check_dev(self.w, prm, ptrs[0], n, out)
+            ok = True
+            for i, el in enumerate(elements):
+                if el["kernel"] == "check":
+                    got = el["out"].download((el["count"],), dtype=np.uint32).tolist()
+                else:
+                    got = self.pts_ints(el["out"].download((el["count"], 2, 4)))
+                if got != el["want"]:
+                    bad = [j for j, (g, x) in enumerate(zip(got, el["want"])) if g != x]
+                    info.update(what=f"launch {i} ({el['kernel']})", first_bad_lane=bad[0], bad_lanes=len(bad))
+                    ok = False
+                    break
+        finally:
+            for b in bufs:
+                b.free()
+        for el in elements:
+            self.hit("edwards.kernel." + el["kernel"])
+            self.hit("edwards.params." + el["set"]["name"])
+            self.hit("edwards.alias." + el["alias"])
+        if len(elements) > 1:
+            self.hit("edwards.chain")
+        if table:
+            self.hit("edwards.table rebuilt without sync")
+        return ok, info
+
+    SCHNORR_DEFECTS = ["none", "s+1", "s+l", "message", "pk", "R off curve", "pk off curve", "pk outside subgroup"]
+
+    def op_schnorr(self):
+        """edwards.keygen, schnorr_sign and schnorr_verify on m <= 6 signatures under a drawn parameter set: keys and signatures against
+        tests/edwards_ref.py, then one drawn defect in one drawn lane and the verdict vector against the reference's schnorr_verify, lane by lane."""
+        from distributed_plonk_amd import edwards as ED
+        from tests import edwards_ref as E
+        rs, curve = self.rs, self.curve
+        r, l = E.MODULI[curve], E.PARAMS[curve]["l"]
+        m = int(rs.randint(1, 7))
+        pset = self.ed_param_set()
+        prm, ref = pset["prm"], pset["ref"]
+        sks, nonces, msgs = ([1 + self.big(r - 1) for _ in range(m)] for _ in range(3))
+        if rs.rand() < 0.3:
+            msgs[int(rs.randint(0, m))] = 0
+        defect = self.SCHNORR_DEFECTS[int(rs.randint(0, len(self.SCHNORR_DEFECTS)))]
+        lane = int(rs.randint(0, m))
+        info = dict(m=m, params=pset["name"], defect=defect, lane=lane)
+        G = (ref or E.PARAMS[curve])["G"]
+        want_pk = [E.mul(curve, sk, G, ref) for sk in sks]
+        want_sig = [E.schnorr_sign(curve, sk, k, msg, ref) for sk, k, msg in zip(sks, nonces, msgs)]
+        pk = ED.keygen(self.w, prm, self.limbs(sks))
+        info["what"] = "keygen"
+        if self.pts_ints(pk) != want_pk:
+            return False, info
+        R, s = ED.schnorr_sign(self.w, prm, self.limbs(sks), self.limbs(nonces), self.limbs(msgs))
+        info["what"] = "sign"
+        if self.pts_ints(R) != [x for x, _ in want_sig] or self.ints(s) != [x for _, x in want_sig]:
+            return False, info
+        pks, Rs, ss, ms = list(want_pk), [x for x, _ in want_sig], [x for _, x in want_sig], list(msgs)
+        if defect == "s+l" and ss[lane] + l >= r:
+            defect = info["defect"] = "s+1"
+        if defect == "s+1":
+            ss[lane] = (ss[lane] + 1) % l
+        elif defect == "s+l":
+            ss[lane] += l
+        elif defect == "message":
+            ms[lane] = (ms[lane] + 1 + self.big(r - 1)) % r
+        elif defect == "pk":
+            pks[lane] = want_pk[(lane + 1) % m] if m > 1 else E.mul(curve, 2, pks[lane], ref)
+        elif defect == "R off curve":
+            Rs[lane] = (Rs[lane][0], (Rs[lane][1] + 1) % r)
+        elif defect == "pk off curve":
+            pks[lane] = ((pks[lane][0] + 1) % r, pks[lane][1])
+        elif defect == "pk outside subgroup":                         # + a point of order 2, 4 or 8, carried to the set's curve
+            T = self.ed_pool()["small"][int(rs.choice([2, 4, 8]))]
+            pks[lane] = E.add(curve, pks[lane], pset["to_set"](T), ref)
+        want = [E.schnorr_verify(curve, pks[i], ms[i], (Rs[i], ss[i]), ref) for i in range(m)]
+        got = ED.schnorr_verify(self.w, prm, self.pts_limbs(pks), self.limbs(ms), (self.pts_limbs(Rs), self.limbs(ss)))
+        info.update(what="verify", want=want)
+        ok = got.tolist() == want
+        if defect == "none":
+            ok = ok and all(want)
+        elif defect not in ("pk", "pk outside subgroup") or m > 1:   # the reference itself must refuse the spoiled lane, and only that one
+            ok = ok and want == [i != lane for i in range(m)]
+        self.hit("schnorr.defect." + defect)
+        self.hit("schnorr.params." + pset["name"])
+        return bool(ok), info
+
+    GADGETS = ["point_add", "point_double", "point_neg", "point_select", "enforce_on_curve"]
+
+    def op_edwards_gadgets(self):
+        """A chain of one to four of the builder's point gadgets on one to three drawn points, optionally one scalar_mul or fixed_base_mul
+        over at most 16 bits, the result enforced equal to two public inputs: solved by solve_dev against HintRefSolver variable for
+        variable, with the level and evaluation counters; by coin carried into preprocess(check=True), whose verdict must be the reference's;
+        half the time one input is spoiled (the first point moved off the curve under enforce_on_curve, or the select bit flipped), and the
+        device must then name the reference's first unsatisfied gate."""
+        import random
+        from distributed_plonk_amd import builder as BD
+        from distributed_plonk_amd import circuit as CI
+        from tests import edwards_ref as E
+        from tests.hint_ref import GIVEN, HintRefSolver
+        rs, curve, pool = self.rs, self.curve, self.ed_pool()
+        r = E.MODULI[curve]
+        cap = 1 << min(self.max_log, 12)
+        pset = self.ed_param_set()
+        prm, ref, to_set = pset["prm"], pset["ref"], pset["to_set"]
+        rnd = random.Random(self.seed())
+        npts = int(rs.randint(1, 4))
+        pts = [to_set(pool["points"][int(rs.randint(0, len(pool["points"])))] if rs.rand() < 0.5 else E.random_point(curve, rnd)) for _ in range(npts)]
+        chain = [self.GADGETS[int(rs.randint(0, len(self.GADGETS)))] for _ in range(int(rs.randint(1, 5)))]
+        spoil = str(rs.choice(["none", "none", "off curve", "select bit"]))
+        if spoil == "off curve" and "enforce_on_curve" not in chain:
+            chain[0] = "enforce_on_curve"                             # on the first point as it came in
+        if spoil == "select bit" and "point_select" not in chain:
+            chain[-1] = "point_select"
+        mul_kind = str(rs.choice(["none", "scalar_mul", "fixed_base_mul"]))
+        per_bit = dict(scalar_mul=21, fixed_base_mul=9).get(mul_kind, 0)
+        nbits = min(16, (cap - 64) // per_bit) if per_bit else 0    # 36 gates for the chain at most, the constants, the IO and constraint gates
+        if nbits < 1:
+            mul_kind, nbits = "none", 0
+        else:
+            nbits = int(rs.randint(1, nbits + 1))
+        k = self.big(1 << nbits) if nbits else 0
+        bit = int(rs.randint(0, 2))
+        info = dict(params=pset["name"], points=npts, chain=chain, mul=mul_kind, nbits=nbits, spoil=spoil)
+
+        b = BD.CircuitBuilder(curve)
+        out_x, out_y = b.public_input(2)
+        coords = [int(v) for v in np.atleast_1d(b.input(2 * npts))]
+        var_pts = [(coords[2 * i], coords[2 * i + 1]) for i in range(npts)]
+        v_bit, v_k = b.input(), b.input()
+        b.enforce_bool(v_bit)
+        cur, cur_val = var_pts[0], pts[0]
+        for j, name in enumerate(chain):
+            other, other_val = var_pts[(j + 1) % npts], pts[(j + 1) % npts]
+            if name == "point_add":
+                cur, cur_val = b.point_add(cur, other, prm), E.add(curve, cur_val, other_val, ref)
+            elif name == "point_double":
+                cur, cur_val = b.point_double(cur, prm), E.add(curve, cur_val, cur_val, ref)
+            elif name == "point_neg":
+                cur, cur_val = b.point_neg(cur), E.neg(curve, cur_val)
+            elif name == "point_select":
+                cur, cur_val = b.point_select(v_bit, cur, other), (cur_val if bit else other_val)
+            else:
+                b.enforce_on_curve(cur, prm)
+        if mul_kind != "none":
+            bits = b.to_bits(v_k, nbits)
+            if mul_kind == "scalar_mul":
+                term, term_val = b.scalar_mul(bits, cur, prm), E.mul(curve, k, cur_val, ref)
+            else:
+                term, term_val = b.fixed_base_mul(bits, prm), E.mul(curve, k, (ref or E.PARAMS[curve])["G"], ref)
+            cur, cur_val = b.point_add(cur, term, prm), E.add(curve, cur_val, term_val, ref)
+        b.enforce_equal(cur[0], out_x)
+        b.enforce_equal(cur[1], out_y)
+        built = b.build()
+        info["n"] = built.n
+        assert built.n <= cap, (built.n, cap)
+        values = [v for P in pts for v in P] + [bit, k]
+        if spoil == "off curve":
+            values[0] = (values[0] + 1 + self.big(r - 1)) % r
+        elif spoil == "select bit":
+            values[2 * npts] = 1 - bit
+        publics = list(cur_val)
+        ref_solver = HintRefSolver(built, values, publics)
+        want, _ = ref_solver.solve()
+        unsat = ref_solver.unsatisfied_gates(want)
+        info.update(first_unsatisfied=unsat[0] if unsat else -1)
+        try:
+            if spoil == "none" and unsat:                             # the generator's own promise: the unspoiled circuit holds
+                info["what"] = "the reference finds the unspoiled circuit unsatisfied"
+                return False, info
+            in_limbs, pub_limbs = self.limbs(values), self.limbs(publics)
+            s = built.solve_dev(self.w, in_limbs, pub_limbs)
+            try:
+                info["what"] = "solve"
+                ok = (np.array_equal(s.witness(), ref_solver.limbs(want)) and s.levels == ref_solver.depth()
+                      and s.evaluations == int((built.def_gate != GIVEN).sum()))
+            finally:
+                s.close()
+            checked = ok and (spoil != "none" or rs.rand() < 0.5)
+            if checked:
+                info["what"] = "preprocess"
+                try:
+                    built.preprocess(self.w, in_limbs, pub_limbs, check=True).close()
+                    ok = not unsat
+                except CI.UnsatisfiedCircuit as ex:
+                    info["reported"] = ex.gate
+                    ok = bool(unsat) and ex.gate == unsat[0] and ex.position == -1
+        finally:
+            built.close()
+        for name in set(chain) | ({mul_kind} - {"none"}):
+            self.hit("gadget." + name)
+        self.hit("gadget.params." + pset["name"])
+        if checked:
+            self.hit("gadget.preprocess " + ("refused" if unsat else "accepted"))
+        if spoil != "none" and unsat:
+            self.hit("gadget.spoil." + spoil)
+        return bool(ok), info
+
+    REPLAY_K = (1, 2, 3, 5, 8)
+
+    def op_replay(self):
+        """plonk_circuit_schedule_dev and plonk_circuit_replay_dev on a layered circuit of op_solve's shapes: the recorded order, segments and
+        counters against the restatement from the reference's levels (tests/replay_ref.py); K witnesses replayed under two drawn fuse widths
+        around the circuit's most frequent segment length, inputs from host arrays or a device buffer by coin, each witness limb for limb
+        against HintRefSolver on its own row, the two replays byte for byte against each other; in a quarter of the draws a planted cycle
+        first, which schedule must report by its smallest variable before a good schedule and replay on the same worker."""
+        from distributed_plonk_amd import circuit as CI
+        from tests.circuit_cases import layered_circuit
+        from tests.hint_ref import GIVEN, HintRefSolver
+        from tests.replay_ref import plan_branches, ref_schedule
+        rs, p = self.rs, self.f.p
+        hints = bool(rs.randint(0, 2))
+        max_gates = 1 << min(self.max_log, 12)
+        widths = [x for x in (1, 63, 64, 65, 255, 256, 257) if 3 * x + 8 <= max_gates]
+        width = int(rs.choice(widths)) if rs.rand() < 0.8 else int(rs.randint(1, max(2, max_gates // 4)))
+        depth = int(rs.randint(1, 301))
+        K = int(rs.choice(self.REPLAY_K))
+        cycle = rs.rand() < 0.25
+        from_device = bool(rs.randint(0, 2))
+        cseed = self.seed()
+        built, inputs, publics = layered_circuit(self.curve, depth, width, cseed, hints, max_gates)
+        info = dict(hints=hints, width=width, depth=depth, cseed=cseed, n=built.n, K=K, cycle=cycle, device_inputs=from_device)
+        ins = [list(inputs)] + [[self.big(p) for _ in inputs] for _ in range(K - 1)]
+        pubs = [list(publics)] + [[self.big(p) for _ in publics] for _ in range(K - 1)]
+        if built.has_hints:                                           # zeros under the inverses and quotients of one row
+            row = ins[int(rs.randint(0, K))]
+            for i in np.flatnonzero(rs.rand(len(row)) < 0.5):
+                row[int(i)] = 0
+        refs = [HintRefSolver(built, i, pu) for i, pu in zip(ins, pubs)]
+        wants = [rf.solve()[0] for rf in refs]
+        ref = refs[0]
+        d_in = None
+        batches = []
+        try:
+            if cycle:
+                defined = np.flatnonzero(built.def_gate != GIVEN)
+                defined = np.array([v for v in defined[defined >= 2] if built.def_gate[v] >= built.num_public], dtype=np.int64)
+                planted = self.planted_cycle(built, ref, defined) if defined.size else None
+                if planted:
+                    cyc, x, y = planted
+                    info.update(x=x, y=y, what="cycle")
+                    try:
+                        cyc.schedule(self.w)
+                        return False, info
+                    except CI.UnsolvableCircuit as ex:
+                        if ex.variable != x:
+                            info["reported"] = ex.variable
+                            return False, info
+                    finally:
+                        cyc.close()
+                    self.hit("replay.cycle")
+            info["what"] = "schedule"
+            try:
+                sched = built.schedule(self.w)
+            except CI.UnsolvableCircuit as ex:                        # no cycle in this circuit: the reference has just solved it
+                info["unsolvable"] = ex.variable
+                return False, info
+            order, seg, levels, evaluations = ref_schedule(built, ref)
+            info.update(levels=levels)
+            if not ((sched.levels, sched.evaluations) == (levels, evaluations) and np.array_equal(sched.seg, seg) and np.array_equal(sched.order(), order)):
+                return False, info
+            lens = np.diff(seg.astype(np.int64))
+            vals, freq = np.unique(lens[lens > 0], return_counts=True)
+            w_len = int(vals[np.argmax(freq)])
+            cands = sorted({0, 1, w_len - 1, w_len, w_len + 1, 64, 256, 4096})
+            fws = [cands[int(i)] for i in rs.permutation(len(cands))[:2]]
+            info.update(w=w_len, fuse_widths=fws)
+            in_limbs = np.stack([ref.limbs(i) for i in ins])
+            pub_limbs = np.stack([ref.limbs(pu) for pu in pubs])
+            if from_device:
+                d_in = self.up(in_limbs)
+            for fw in fws:
+                if from_device:
+                    batches.append(built.solve_many_dev(self.w, public_inputs=pub_limbs, d_inputs=d_in.ptr, fuse_width=fw))
+                else:
+                    batches.append(built.solve_many_dev(self.w, in_limbs, pub_limbs, fuse_width=fw))
+            got = [[bt.witness(k_) for k_ in range(K)] for bt in batches]
+            ok = True
+            for fw, g in zip(fws, got):
+                for k_ in range(K):
+                    if not np.array_equal(g[k_], ref.limbs(wants[k_])):
+                        info.update(what="replay", fuse_width=fw, witness=k_)
+                        ok = False
+            if ok and not all(np.array_equal(a, b_) for a, b_ in zip(got[0], got[1])):
+                info.update(what="two fuse widths")
+                ok = False
+        finally:
+            for bt in batches:
+                bt.close()
+            if d_in is not None:
+                d_in.free()
+            built.close()
+        for fw in fws:
+            for name in plan_branches(seg, fw, K):
+                self.hit("replay." + name)
+        self.hit("replay.inputs from " + ("the device" if from_device else "the host"))
+        self.hit("replay.hints" if built.has_hints else "replay.no hints")
+        return bool(ok), info
+
     CORE_OPS = ["ntt", "coset_eval_interp", "msm", "commit_many", "poly", "lincomb", "perm_product", "transpose", "distributed_fft", "quotient", "compact_rows_fft", "round1", "prove_verify", "class_prove", "msm_table",
                 "perm_product_ranges", "class_ifft", "init_refuses_bad_srs", "trim"]
     CIRCUIT_OPS = ["circuit_preprocess", "solve", "rescue", "accumulator", "verify_batch", "membership"]
-    OPS = CORE_OPS + CIRCUIT_OPS
-    GROUPS = {"core": CORE_OPS, "circuit": CIRCUIT_OPS}
+    CURVE_OPS = ["edwards", "schnorr", "edwards_gadgets", "replay"]
+    OPS = CORE_OPS + CIRCUIT_OPS + CURVE_OPS
+    GROUPS = {"core": CORE_OPS, "circuit": CIRCUIT_OPS, "curve": CURVE_OPS}
 
     def close(self):
         for built in self.membership_built.values():
@@ -1277,8 +1824,9 @@ class Fuzz:
 
 
 def parse_ops(spec):
-    """--ops: operation names and the groups "core" (the MSM / NTT / prover side, nineteen operations) and "circuit" (circuits, witnesses,
-    Rescue trees, the verifier) -> the list that every draw indexes, in the order given, duplicates dropped"""
+    """--ops: operation names and the groups "core" (the MSM / NTT / prover side, nineteen operations), "circuit" (circuits, witnesses,
+    Rescue trees, the verifier) and "curve" (the embedded Edwards curve, signatures, point gadgets, schedule replay) -> the list that every
+    draw indexes, in the order given, duplicates dropped"""
     names = []
     for part in (x.strip() for x in spec.split(",")):
         for name in Fuzz.GROUPS.get(part, [part]):
@@ -1311,7 +1859,11 @@ def run(seconds, seed, curves, max_log, only=None, max_ops=None, verbose=True, o
         for f in fz:
             f.close()
     if verbose:
-        print(f"fuzz ok: {it} operations, no mismatch; per op {counts}", flush=True)
+        branches = {}
+        for f in fz:
+            for name, hits in f.branches.items():
+                branches[name] = branches.get(name, 0) + hits
+        print(f"fuzz ok: {it} operations, no mismatch; per op {counts}; branches {dict(sorted(branches.items()))}", flush=True)
     return 0, counts
 
 
@@ -1322,7 +1874,7 @@ if __name__ == "__main__":
     ap.add_argument("--curve", default="both", choices=["bn254", "bls12_381", "both"])
     ap.add_argument("--max-log", type=int, default=13)
     ap.add_argument("--only", default=None, choices=Fuzz.OPS)
-    ap.add_argument("--ops", default=None, help="comma-separated operation names and groups (core, circuit) to draw from; default: all")
+    ap.add_argument("--ops", default=None, help="comma-separated operation names and groups (core, circuit, curve) to draw from; default: all")
     ap.add_argument("--max-ops", type=int, default=None)
     ap.add_argument("--trace", action="store_true", help="print every operation and its parameters as it finishes")
     a = ap.parse_args()
