@@ -30,6 +30,11 @@ addition law needs no case distinction and hence no selector of its own — `poi
 `enforce_on_curve`, `to_bits_strict` (every bit of the canonical residue), `scalar_mul`, `fixed_base_mul` and `schnorr_verify` are composed
 from `mul`, `mul_add`, `lc` and `div`; edwards.py computes the same group on the device and `edwards.schnorr_circuit` builds the circuit.
 
+Vectors and encryption: `rescue_sponge` hashes a list of variables (the sponge of rescue.py: the length sits in the capacity),
+`rescue_stream` gives the counter-mode keystream under a key variable, and `elgamal_encrypt` proves a ciphertext of elgamal.py —
+E = [r] G, the key from [r] ek, the stream added to the message — from `fixed_base_mul`, `scalar_mul` and the two; `elgamal.elgamal_circuit`
+builds the circuit.
+
 Same circuit, next witness: `BuiltCircuit.schedule` records the solver's order of evaluation once (plonk_circuit_schedule_dev),
 `solve_many_dev` replays it for K witnesses in one go (plonk_circuit_replay_dev; each witness bit-identical to solve_dev's), and `setup`
 gives a `circuit.CircuitKey` — permutation and proving key, once — whose `instances(batch)` are what `Prover.prove_dev` takes per witness.
@@ -669,6 +674,38 @@ class CircuitBuilder:
             cur = self.rescue_hash3(l, mid, r, prm)
         return cur
 
+    def rescue_sponge(self, inputs, n_out: int = 1, params=None):
+        """sponge(x_0 .. x_{L-1}; n_out) of rescue.py, the variable-length hash: s = (0, 0, 0, L), then per block of three s[j] += x[3b + j]
+        and s = rescue_permutation(s); -> the LIST of the n_out first state variables after the last block, n_out in (1, 2, 3).  The first
+        block goes straight into rescue_permutation([x0, x1, x2, constant(L)]) with zero for absent elements; each later block is up to three
+        add gates and one permutation: 148 ceil(L / 3) + max(L - 3, 0) gates per instance (and at most one for the constant L), in
+        37 + 38 (ceil(L / 3) - 1) levels.  The length in the capacity separates (a) from (a, 0); rescue_sponge([a, b, c])[0] is
+        permute((a, b, c, 3))[0] and NOT rescue_hash3(a, b, c) = permute((a, b, c, 0))[0], by design."""
+        inputs = list(inputs)
+        L = len(inputs)
+        if not 1 <= L < 1 << 32:
+            raise ValueError(f"rescue_sponge: L = {L} inputs (1 .. 2^32 - 1)")
+        if n_out not in (1, 2, 3):
+            raise ValueError(f"rescue_sponge: n_out = {n_out!r} (1, 2 or 3)")
+        prm = self._rescue_params(params)
+        x = self._same_length(inputs)
+        s = self.rescue_permutation([x[j] if j < L else self.zero for j in range(3)] + [self.constant(L)], prm)
+        for b in range(1, (L + 2) // 3):
+            s = [self.add(s[j], x[3 * b + j]) if 3 * b + j < L else s[j] for j in range(3)] + [s[3]]
+            s = self.rescue_permutation(s, prm)
+        return s[:n_out]
+
+    def rescue_stream(self, key, nblocks: int, params=None):
+        """The keystream of rescue.py's counter mode under the variable `key`: -> a list of nblocks triples, block j being the three first
+        variables of rescue_permutation([key, constant(j), zero, constant(-1)]).  148 gates per block and instance (and the constants), every
+        block at the same depth: 37 levels.  Element i of a text takes block i div 3, position i mod 3."""
+        if not isinstance(nblocks, _SCALARS) or not 1 <= int(nblocks) < 1 << 32:
+            raise ValueError(f"rescue_stream: nblocks = {nblocks!r} (1 .. 2^32 - 1)")
+        prm = self._rescue_params(params)
+        key = self._var(key)
+        minus_one = self.constant(-1)
+        return [tuple(self.rescue_permutation([key, self.constant(j), self.zero, minus_one], prm)[:3]) for j in range(int(nblocks))]
+
     # ------------------------------------------------------------------ the embedded Edwards curve (edwards.py: the same group on the device)
     # A point is a pair (x_ids, y_ids).  E: a x^2 + y^2 = 1 + d x^2 y^2 with a a square and d a non-square, so for points ON E no denominator
     # below is zero and one formula serves P + Q, P + P, P - P, the identity (0, 1) and the points of small order.  The gadgets are gates the
@@ -845,6 +882,41 @@ class CircuitBuilder:
         lhs = self.fixed_base_mul(s_bits, prm)
         rhs = self.point_add(R, self.scalar_mul(c_bits, pk, prm), prm)
         self.enforce_point_equal(lhs, rhs)
+
+    def elgamal_encrypt(self, ek, msg, r, prm=None, rescue=None):
+        """The ciphertext of elgamal.encrypt on the message variables `msg` (a list of L >= 1) under the key point ek with the randomness r:
+        E = [r] G, S = [r] ek, k = hash3(S.x, S.y, 0), ct_i = msg_i + ks_{i div 3}[i mod 3] with the keystream of rescue_stream under k.
+        -> (E, ct): the point E and the list of the L ciphertext variables; the caller equates them with the public ciphertext.  r: a
+        variable (decomposed here with to_bits to bit_length(l) bits), or a LIST of that many bit variables, LSB first (made boolean here),
+        as schnorr_verify takes s.  to_bits, fixed_base_mul, scalar_mul, rescue_hash3, rescue_stream over ceil(L / 3) blocks and L add
+        gates: 6987 + 148 ceil(L / 3) + L gates per instance on bn254, 7014 + ... on bls12_381 with the default parameters (and the
+        constants of the stream), in 4 bit_length(l) + 75 levels.
+        NOT proved: that ek is on E and in the subgroup of order l — ek is public, check it outside with edwards.in_subgroup, as the
+        doublings of scalar_mul assume ek on E; that r < l — any r below 2^bit_length(l) is accepted (elgamal.encrypt refuses r >= l).
+        The SAME bits of r serve both multiplications, which is the point: E and the key belong to one r."""
+        prm, rp = self._edwards_params(prm), self._rescue_params(rescue)
+        msg = list(msg)
+        L = len(msg)
+        if not 1 <= L < 1 << 32:
+            raise ValueError(f"elgamal_encrypt: a message of {L} elements (at least 1)")
+        lbits = prm.order.bit_length()
+        r_is_bits = isinstance(r, (list, tuple))
+        if r_is_bits and len(r) != lbits:
+            raise ValueError(f"r: {len(r)} bits, the order has {lbits}")
+        self._nbits(lbits, self.field.p.bit_length() - 1)
+        (ek,), rest = self._points([ek], msg + (list(r) if r_is_bits else [r]))
+        msg, r = rest[:L], rest[L:]
+        if r_is_bits:
+            bits = list(r)
+            for b in bits:
+                self.enforce_bool(b)
+        else:
+            bits = self.to_bits(r[0], lbits)
+        E = self.fixed_base_mul(bits, prm)
+        S = self.scalar_mul(bits, ek, prm)
+        k = self.rescue_hash3(S[0], S[1], self.zero, rp)
+        ks = self.rescue_stream(k, (L + 2) // 3, rp)
+        return E, [self.add(msg[i], ks[i // 3][i % 3]) for i in range(L)]
 
     # ------------------------------------------------------------------ constraints
     def enforce_equal(self, a, b):

@@ -1482,6 +1482,59 @@ extern "C" int plonk_edwards_check_dev(plonk_ctx* ctx, const uint64_t* params, c
     if (count == 0) return PLONK_OK;
     return edwards_check_run(ctx->curve, params, (const Fr*)d_points, count, (uint32_t*)d_flags, ctx->stream, "plonk_edwards_check_dev");
 }
+// ---- the Rescue sponge and stream, and the ElGamal shared key (elgamal_kernels.hpp).  Every argument is checked before rescue_params() uploads
+// anything, so a refused call enqueues nothing.
+static int elgamal_text_shape(size_t L, size_t count, const char* who) {
+    if (L == 0 || (uint64_t)L > 0xFFFFFFFFull) return plonk_fail(PLONK_ERR_ARG, "%s: L = %zu (1 .. 2^32 - 1)", who, L);
+    if ((uint64_t)count > ELGAMAL_MAX_LANES / (((uint64_t)L + 2) / 3) || (uint64_t)count > (0xFFFFFFFFFFFFFFFFull / 32) / L)
+        return plonk_fail(PLONK_ERR_ARG, "%s: count = %zu texts of L = %zu elements exceed one launch (2^31 - 1 workgroups of %u lanes)", who, count, L,
+                          (unsigned)ELGAMAL_LANES_PER_GROUP);
+    return PLONK_OK;
+}
+extern "C" int plonk_rescue_sponge_dev(plonk_ctx* ctx, const uint64_t* params, const void* d_inputs, size_t L, size_t count, unsigned n_out, void* d_out) {
+    CHECK_CTX(ctx);
+    if (!params) return plonk_fail(PLONK_ERR_ARG, "plonk_rescue_sponge_dev: params is null");
+    if (!d_inputs) return plonk_fail(PLONK_ERR_ARG, "plonk_rescue_sponge_dev: d_inputs is null");
+    if (!d_out) return plonk_fail(PLONK_ERR_ARG, "plonk_rescue_sponge_dev: d_out is null");
+    if (n_out < 1 || n_out > 3) return plonk_fail(PLONK_ERR_ARG, "plonk_rescue_sponge_dev: n_out = %u (1 .. 3)", n_out);
+    int rc = elgamal_text_shape(L, 0, "plonk_rescue_sponge_dev");
+    if (rc) return rc;
+    if ((uint64_t)count > ELGAMAL_MAX_LANES || (uint64_t)count > (0xFFFFFFFFFFFFFFFFull / 32) / L)
+        return plonk_fail(PLONK_ERR_ARG, "plonk_rescue_sponge_dev: count = %zu messages of L = %zu elements exceed one launch (2^31 - 1 workgroups of %u lanes)", count, L,
+                          (unsigned)ELGAMAL_LANES_PER_GROUP);
+    if (count == 0) return PLONK_OK;
+    if ((rc = rescue_params(ctx, params))) return rc;
+    return rescue_sponge_run(ctx->curve, ctx->d_rescue, (const Fr*)d_inputs, L, count, n_out, (Fr*)d_out, ctx->stream, "plonk_rescue_sponge_dev");
+}
+extern "C" int plonk_rescue_stream_dev(plonk_ctx* ctx, const uint64_t* params, const void* d_keys, const void* d_in, size_t L, size_t count, int decrypt, void* d_out) {
+    CHECK_CTX(ctx);
+    if (!params) return plonk_fail(PLONK_ERR_ARG, "plonk_rescue_stream_dev: params is null");
+    if (!d_keys) return plonk_fail(PLONK_ERR_ARG, "plonk_rescue_stream_dev: d_keys is null");
+    if (!d_in) return plonk_fail(PLONK_ERR_ARG, "plonk_rescue_stream_dev: d_in is null");
+    if (!d_out) return plonk_fail(PLONK_ERR_ARG, "plonk_rescue_stream_dev: d_out is null");
+    int rc = elgamal_text_shape(L, count, "plonk_rescue_stream_dev");
+    if (rc) return rc;
+    if (count == 0) return PLONK_OK;
+    if ((rc = rescue_params(ctx, params))) return rc;
+    return rescue_stream_run(ctx->curve, ctx->d_rescue, (const Fr*)d_keys, (const Fr*)d_in, L, count, decrypt, (Fr*)d_out, ctx->stream, "plonk_rescue_stream_dev");
+}
+extern "C" int plonk_edwards_dh_key_dev(plonk_ctx* ctx, const uint64_t* edwards_params, const uint64_t* rescue_params_, const void* d_scalars, const void* d_points,
+                                        size_t count, void* d_keys) {
+    CHECK_CTX(ctx);
+    if (!edwards_params) return plonk_fail(PLONK_ERR_ARG, "plonk_edwards_dh_key_dev: edwards_params is null");
+    if (!rescue_params_) return plonk_fail(PLONK_ERR_ARG, "plonk_edwards_dh_key_dev: rescue_params is null");
+    if (!d_scalars) return plonk_fail(PLONK_ERR_ARG, "plonk_edwards_dh_key_dev: d_scalars is null");
+    if (!d_points) return plonk_fail(PLONK_ERR_ARG, "plonk_edwards_dh_key_dev: d_points is null");
+    if (!d_keys) return plonk_fail(PLONK_ERR_ARG, "plonk_edwards_dh_key_dev: d_keys is null");
+    if ((uint64_t)count > ELGAMAL_MAX_LANES)
+        return plonk_fail(PLONK_ERR_ARG, "plonk_edwards_dh_key_dev: count = %zu exceeds one launch (2^31 - 1 workgroups of %u pairs)", count, (unsigned)ELGAMAL_LANES_PER_GROUP);
+    if (count == 0) return PLONK_OK;
+    int rc = ensure_scratch2(ctx, count * 64);          // the shared points between the two launches; a larger buffer replaces a smaller one behind a device-wide wait
+    if (rc) return rc;
+    if ((rc = rescue_params(ctx, rescue_params_))) return rc;
+    return edwards_dh_key_run(ctx->curve, edwards_params, ctx->d_rescue, (const Fr*)d_scalars, (const Fr*)d_points, count, (Fr*)d_keys, (Fr*)ctx->d_scratch2, ctx->stream,
+                              "plonk_edwards_dh_key_dev");
+}
 extern "C" int plonk_debug_field_op(plonk_ctx* ctx, int field, int op, const uint64_t* a, const uint64_t* b, uint64_t* out, size_t n) {
     CHECK_CTX(ctx);
     if (!a || !out) return plonk_fail(PLONK_ERR_ARG, "plonk_debug_field_op: null");

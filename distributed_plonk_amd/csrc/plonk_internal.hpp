@@ -275,6 +275,14 @@ int edwards_mul_run(int curve, const uint64_t* params, const Fr* d_scalars, cons
 int edwards_fixed_mul_run(int curve, const uint64_t* params, const Fr* d_scalars, size_t count, const Fr* d_table, Fr* d_out, hipStream_t stream, const char* who);
 int edwards_add_run(int curve, const uint64_t* params, const Fr* d_p, const Fr* d_q, size_t count, Fr* d_out, hipStream_t stream, const char* who);
 int edwards_check_run(int curve, const uint64_t* params, const Fr* d_points, size_t count, uint32_t* d_flags, hipStream_t stream, const char* who);
+// The Rescue sponge, the counter-mode stream and the ElGamal shared key (elgamal_kernels.hpp, built in synth.hip).  d_params / d_rescue: the 116
+// Rescue Fr on the device; L >= 1, 1 <= n_out <= 3, count >= 1; in / out: [count][L] Fr (sponge out: [count][n_out]); keys: [count] Fr; shared: [count][2] Fr of working space.  Enqueued only.
+constexpr uint64_t ELGAMAL_LANES_PER_GROUP = 256, ELGAMAL_MAX_LANES = 0x7FFFFFFFull * ELGAMAL_LANES_PER_GROUP;          // what one launch holds
+int rescue_sponge_run(int curve, const Fr* d_params, const Fr* d_in, uint64_t L, uint64_t count, unsigned n_out, Fr* d_out, hipStream_t stream, const char* who);
+int rescue_stream_run(int curve, const Fr* d_params, const Fr* d_keys, const Fr* d_in, uint64_t L, uint64_t count, int decrypt, Fr* d_out, hipStream_t stream,
+                      const char* who);
+int edwards_dh_key_run(int curve, const uint64_t* params, const Fr* d_rescue, const Fr* d_scalars, const Fr* d_points, size_t count, Fr* d_keys, Fr* d_shared,
+                       hipStream_t stream, const char* who);
 
 // ----------------------------------------------------------------------------------------------- O(n) prover steps (poly_ops.hip, quotient.hip)
 int quotient_evals_run(NttTables& T, const plonk_quotient_inputs* in, size_t n, size_t m, const uint64_t* alpha, const uint64_t* beta,

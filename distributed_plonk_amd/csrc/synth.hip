@@ -366,6 +366,8 @@ int synth_circuit_dev(int curve, uint64_t seed, size_t n, size_t num_inputs, con
 #include "rescue_acc_kernels.hpp"
 // the embedded twisted Edwards curve over Fr: scalar multiplication, addition and the curve / subgroup check, on the same power for the inversion
 #include "edwards_kernels.hpp"
+// the Rescue sponge and counter-mode stream, and the ElGamal shared key [scalar] point -> hash3: the two bodies above in one lane
+#include "elgamal_kernels.hpp"
 
 // ---------------------------------------------------------------------------------------------- batched proof verification
 // the per-proof work of jf-plonk's verify / batch_verify up to the pairing: kernels and launcher in their own header

@@ -1,6 +1,7 @@
-"""The Rescue permutation, Merkle trees and the ternary accumulator over it, computed on the device (csrc/rescue_kernels.hpp and
-csrc/rescue_acc_kernels.hpp behind plonk_rescue_permute_dev, plonk_rescue_merkle_dev, plonk_rescue_acc_build_dev and
-plonk_rescue_acc_paths_dev), with the parameters that `builder.CircuitBuilder.rescue_permutation` proves the same function with.
+"""The Rescue permutation, Merkle trees, the ternary accumulator, the sponge and the counter-mode stream over it, computed on the device
+(csrc/rescue_kernels.hpp, csrc/rescue_acc_kernels.hpp and csrc/elgamal_kernels.hpp behind plonk_rescue_permute_dev, plonk_rescue_merkle_dev,
+plonk_rescue_acc_build_dev, plonk_rescue_acc_paths_dev, plonk_rescue_sponge_dev and plonk_rescue_stream_dev), with the parameters that
+`builder.CircuitBuilder.rescue_permutation` proves the same function with.
 
 State s in Fr^4, MDS matrix M (4 x 4), round keys K[0 .. 24] (4 elements each), alpha = 5 on both scalar fields — the structure of
 jellyfish's jf-rescue (width 4, 12 rounds, 25 round keys):
@@ -29,6 +30,17 @@ after another from the leaves up (offset_0 = 0, offset_{j+1} = offset_j + c_j), 
 pos_j = floor(i / 3^j) mod 3 and the two OTHER members of its group of three (from 3 floor(i / 3^(j+1)) on, 0 beyond c_j) in ascending
 position as sib1_j, sib2_j; builder.accumulator_root takes them with is_left_j = [pos_j = 0] and is_right_j = [pos_j = 2].  jellyfish's own
 constants and its encoding of a leaf are not pinned here: the parameters are injectable, the structure is the one above.
+
+The fourth state element is the CAPACITY and carries the domain: hash2 and hash3 use 0, the sponge starts at L, the stream uses -1.
+
+    sponge(x_0 .. x_{L-1}; n_out)   1 <= L < 2^32, n_out in (1, 2, 3):   s = (0, 0, 0, L);   for each block b = 0 .. ceil(L / 3) - 1:
+                                    s[j] += x[3b + j] for j < 3 and 3b + j < L, then s = permute(s);   the result is s[0 : n_out]
+    stream                          block j >= 0 of the keystream under key k is ks_j = permute((k, j, 0, -1))[0 : 3]; element i of a text of
+                                    L elements uses ks_{i div 3}[i mod 3]: encryption adds it, decryption subtracts it
+
+The length in the capacity separates (a) from (a, 0) from (a, 0, 0, 0).  sponge((a, b, c); 1) = permute((a, b, c, 3))[0] DIFFERS from
+hash3(a, b, c) = permute((a, b, c, 0))[0], by design: the two are different domains.  builder.rescue_sponge and builder.rescue_stream prove
+the same two functions; elgamal.py encrypts with the stream.
 
 Field elements cross this module as everywhere in the package: (.., 4) uint64 Montgomery limbs.
 """
@@ -291,3 +303,83 @@ class Accumulator:
         for b in (self.d_nodes, self.d_elems):
             if b.ptr:
                 b.free()
+
+
+# ---------------------------------------------------------------------------------------------- the sponge and the counter-mode stream
+MAX_SPONGE_LEN = (1 << 32) - 1
+
+
+def _text_shape(L: int, what: str):
+    if not isinstance(L, (int, np.integer)) or not 1 <= int(L) <= MAX_SPONGE_LEN:
+        raise ValueError(f"{what}: L = {L!r} (1 .. 2^32 - 1)")
+
+
+def sponge_dev(worker: PlonkWorker, params: RescueParams, d_inputs: int, L: int, count: int, n_out: int, d_out: int):
+    """d_out[i][0 : n_out] = sponge(d_inputs[i][0 : L]; n_out): inputs (count, L) Fr row-major, outputs (count, n_out).  One launch, ordered
+    on the worker's stream, not synchronised.  sponge((a, b, c); 1) is NOT hash3(a, b, c): the capacity starts at L = 3, hash3's at 0."""
+    _check(worker, params)
+    _text_shape(L, "sponge")
+    if n_out not in (1, 2, 3):
+        raise ValueError(f"sponge: n_out = {n_out!r} (1, 2 or 3)")
+    worker.rescue_sponge_dev(params.limbs(), d_inputs, int(L), count, n_out, d_out)
+
+
+def sponge(worker: PlonkWorker, params: RescueParams, inputs, n_out: int = 1) -> np.ndarray:
+    """inputs: (count, L, 4) Montgomery limbs, L >= 1 -> (count, n_out, 4): the sponge of each row (see the module docstring; it differs from
+    hash3 on three elements by design)"""
+    _check(worker, params)
+    x = np.ascontiguousarray(inputs, dtype=np.uint64)
+    if x.ndim != 3 or x.shape[2] != 4:
+        raise ValueError(f"sponge: inputs of shape {x.shape}, expected (count, L, 4)")
+    count, L = x.shape[0], x.shape[1]
+    _text_shape(L, "sponge")
+    if n_out not in (1, 2, 3):
+        raise ValueError(f"sponge: n_out = {n_out!r} (1, 2 or 3)")
+    if count == 0:
+        return np.zeros((0, n_out, 4), dtype=np.uint64)
+    d_in = worker.alloc(x.nbytes)
+    d_out = None
+    try:
+        d_out = worker.alloc(count * n_out * 32)
+        d_in.upload(x)
+        sponge_dev(worker, params, d_in.ptr, L, count, n_out, d_out.ptr)
+        return d_out.download((count, n_out, 4))
+    finally:
+        d_in.free()
+        if d_out is not None:
+            d_out.free()
+
+
+def stream_dev(worker: PlonkWorker, params: RescueParams, d_keys: int, d_in: int, L: int, count: int, d_out: int, decrypt: bool = False):
+    """d_out[i][t] = d_in[i][t] + ks (or - ks with decrypt) for the keystream under d_keys[i]: keys (count,) Fr, texts (count, L) Fr row-major.
+    One launch of count x ceil(L / 3) lanes, ordered on the worker's stream, not synchronised; d_out may be d_in."""
+    _check(worker, params)
+    _text_shape(L, "stream")
+    worker.rescue_stream_dev(params.limbs(), d_keys, d_in, int(L), count, bool(decrypt), d_out)
+
+
+def stream(worker: PlonkWorker, params: RescueParams, keys, texts, decrypt: bool = False) -> np.ndarray:
+    """keys (count, 4), texts (count, L, 4) Montgomery limbs -> texts + keystream (decrypt: - keystream), same shape"""
+    _check(worker, params)
+    k = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, 4)
+    x = np.ascontiguousarray(texts, dtype=np.uint64)
+    if x.ndim != 3 or x.shape[2] != 4:
+        raise ValueError(f"stream: texts of shape {x.shape}, expected (count, L, 4)")
+    if k.shape[0] != x.shape[0]:
+        raise ValueError(f"mismatched lengths [{k.shape[0]}, {x.shape[0]}]: one key per text")
+    count, L = x.shape[0], x.shape[1]
+    _text_shape(L, "stream")
+    if count == 0:
+        return x.copy()
+    d_k = worker.alloc(k.nbytes)
+    d_x = None
+    try:
+        d_x = worker.alloc(x.nbytes)
+        d_k.upload(k)
+        d_x.upload(x)
+        stream_dev(worker, params, d_k.ptr, d_x.ptr, L, count, d_x.ptr, decrypt)
+        return d_x.download(x.shape)
+    finally:
+        d_k.free()
+        if d_x is not None:
+            d_x.free()

@@ -498,6 +498,26 @@ class PlonkWorker:
         p = None if params is None else _u64(params)
         check(self.lib.plonk_edwards_check_dev(self.ctx, _ptr(p), d_points or None, count, d_flags or None))
 
+    # ------------------------------------------------------------------ the Rescue sponge and stream, the ElGamal key (rescue.py, elgamal.py)
+    def rescue_sponge_dev(self, params: Optional[np.ndarray], d_inputs: int, L: int, count: int, n_out: int, d_out: int):
+        """d_out[i][0 : n_out] = sponge(d_inputs[i][0 : L]; n_out) (plonk_rescue_sponge_dev); params as for rescue_permute_dev.  Enqueued on the
+        context's stream, not synchronised."""
+        p = None if params is None else _u64(params)
+        check(self.lib.plonk_rescue_sponge_dev(self.ctx, _ptr(p), d_inputs or None, L, count, n_out, d_out or None))
+
+    def rescue_stream_dev(self, params: Optional[np.ndarray], d_keys: int, d_in: int, L: int, count: int, decrypt: bool, d_out: int):
+        """d_out[i][t] = d_in[i][t] +- the Rescue counter-mode keystream under d_keys[i] (plonk_rescue_stream_dev); d_out may be d_in.  Enqueued,
+        not synchronised."""
+        p = None if params is None else _u64(params)
+        check(self.lib.plonk_rescue_stream_dev(self.ctx, _ptr(p), d_keys or None, d_in or None, L, count, 1 if decrypt else 0, d_out or None))
+
+    def edwards_dh_key_dev(self, edwards_params: Optional[np.ndarray], rescue_params: Optional[np.ndarray], d_scalars: int, d_points: int, count: int, d_keys: int):
+        """d_keys[i] = hash3(S.x, S.y, 0) for S = [scalars[i]] points[i] (plonk_edwards_dh_key_dev; 64 count bytes of the context's scratch hold the shared
+        points between its two launches).  Enqueued, not synchronised."""
+        e = None if edwards_params is None else _u64(edwards_params)
+        r = None if rescue_params is None else _u64(rescue_params)
+        check(self.lib.plonk_edwards_dh_key_dev(self.ctx, _ptr(e), _ptr(r), d_scalars or None, d_points or None, count, d_keys or None))
+
     def circuit_scatter_inputs_dev(self, d_input_vars: int, num_inputs: int, d_inputs: int, d_witness: int, num_vars: int):
         """witness[input_vars[k]] = inputs[k] on the device (plonk_circuit_scatter_inputs_dev); d_input_vars: u32.  Synchronises."""
         check(self.lib.plonk_circuit_scatter_inputs_dev(self.ctx, d_input_vars or None, num_inputs, d_inputs or None, d_witness or None, num_vars))

@@ -178,6 +178,9 @@ extern "C" {
     pub fn plonk_edwards_fixed_mul_dev(ctx: *mut plonk_ctx, params: *const u64, d_scalars: *const c_void, count: usize, d_out: *mut c_void) -> c_int;
     pub fn plonk_edwards_add_dev(ctx: *mut plonk_ctx, params: *const u64, d_p: *const c_void, d_q: *const c_void, count: usize, d_out: *mut c_void) -> c_int;
     pub fn plonk_edwards_check_dev(ctx: *mut plonk_ctx, params: *const u64, d_points: *const c_void, count: usize, d_flags: *mut c_void) -> c_int;
+    pub fn plonk_rescue_sponge_dev(ctx: *mut plonk_ctx, rescue_params: *const u64, d_inputs: *const c_void, l: usize, count: usize, n_out: c_uint, d_out: *mut c_void) -> c_int;
+    pub fn plonk_rescue_stream_dev(ctx: *mut plonk_ctx, rescue_params: *const u64, d_keys: *const c_void, d_in: *const c_void, l: usize, count: usize, decrypt: c_int, d_out: *mut c_void) -> c_int;
+    pub fn plonk_edwards_dh_key_dev(ctx: *mut plonk_ctx, edwards_params: *const u64, rescue_params: *const u64, d_scalars: *const c_void, d_points: *const c_void, count: usize, d_keys: *mut c_void) -> c_int;
     pub fn plonk_rescue_acc_paths_dev(ctx: *mut plonk_ctx, d_nodes: *const c_void, count: usize, height: c_uint, d_elems: *const c_void, d_uids: *const c_void, m: usize, d_inputs_out: *mut c_void) -> c_int;
     pub fn plonk_circuit_scatter_inputs_dev(ctx: *mut plonk_ctx, d_input_vars: *const c_void, num_inputs: usize, d_inputs: *const c_void, d_witness: *mut c_void, num_vars: usize) -> c_int;
     pub fn plonk_g2_generator(curve: c_int, out: *mut u64) -> c_int;

@@ -461,6 +461,30 @@ int plonk_edwards_add_dev(plonk_ctx* ctx, const uint64_t* params, const void* d_
 /* d_flags: u32 [count].  Bit 0: the point satisfies the curve equation.  Bit 1: it does and [l] point = (0, 1), i.e. it lies in the subgroup of
  * prime order l (l < r: one run of mul's loop over bit_length(l) bits, without the inversion). */
 int plonk_edwards_check_dev(plonk_ctx* ctx, const uint64_t* params, const void* d_points, size_t count, void* d_flags);
+/* A variable-length hash and public-key encryption over the two families above, the functions builder.py's rescue_sponge, rescue_stream and
+ * elgamal_encrypt prove.  permute is the width-4 Rescue permutation; its fourth state element is the capacity and carries the domain: hash2 and
+ * hash3 use 0, the sponge starts at L, the stream uses -1.  rescue_params: HOST, 116 Fr as for plonk_rescue_permute_dev (uploaded again only when
+ * the bytes differ; the copy is ordered on the stream).  The sponge and the stream are ONE launch each, the key two; all are ordered on the
+ * context's stream and return once the work is enqueued; count = 0 is a no-op.  PLONK_ERR_ARG naming the entry point and the argument — for a NULL pointer, L = 0 or L >= 2^32, n_out outside
+ * 1 .. 3, and a lane count beyond one launch (2^31 - 1 workgroups of 256 lanes) — before anything is uploaded or launched.
+ * sponge: d_out[i][0 : n_out] = s[0 : n_out] after  s = (0, 0, 0, L);  for b < ceil(L / 3):  s[j] += x_i[3b + j] (j < 3, 3b + j < L), s = permute(s).
+ * d_inputs: [count][L] Fr Montgomery, row-major; d_out: [count][n_out] Fr.  One lane per message, ceil(L / 3) permutations each.  The length in
+ * the capacity separates (a) from (a, 0); sponge((a, b, c); 1) = permute((a, b, c, 3))[0] is NOT hash3(a, b, c), by design. */
+int plonk_rescue_sponge_dev(plonk_ctx* ctx, const uint64_t* rescue_params, const void* d_inputs, size_t L, size_t count, unsigned n_out, void* d_out);
+/* Counter mode: block j >= 0 of the keystream under key k is ks_j = permute((k, j, 0, -1))[0 : 3], and element t of a text of L elements uses
+ * ks_{t div 3}[t mod 3].  d_out[i][t] = d_in[i][t] + ks (decrypt = 0) or d_in[i][t] - ks (decrypt != 0) under d_keys[i].  d_keys: [count] Fr;
+ * d_in, d_out: [count][L] Fr, row-major; d_out may be d_in (and must not overlap d_keys).  One lane per (text, block): count x ceil(L / 3) lanes;
+ * exactly count x L elements are written. */
+int plonk_rescue_stream_dev(plonk_ctx* ctx, const uint64_t* rescue_params, const void* d_keys, const void* d_in, size_t L, size_t count, int decrypt, void* d_out);
+/* The shared key of the ElGamal / Rescue hybrid: d_keys[i] = hash3(S.x, S.y, 0) for S = [k_i] d_points[i], scalars and points as for
+ * plonk_edwards_mul_dev.  With ek = [dk] G, encryption under randomness r < l is E = [r] G (plonk_edwards_fixed_mul_dev), key from (r, ek), then
+ * plonk_rescue_stream_dev; decryption takes the key from (dk, E).  One lane per pair, ~21.8 k products, in TWO launches: mul's loop with its one
+ * inversion, then the permutation, with the shared points in a context-owned buffer of 64 count bytes between them (plonk_trim gives it back;
+ * a call that needs a larger one than the last waits for the device while it is replaced).  One kernel doing both was measured 9 % slower
+ * than the two: DESIGN.md §4.3.  A point that does not satisfy the curve equation is taken for the identity (0, 1) —
+ * its key is hash3(0, 1, 0) —; whether a point lies in the subgroup of order l is plonk_edwards_check_dev's verdict, not an error here. */
+int plonk_edwards_dh_key_dev(plonk_ctx* ctx, const uint64_t* edwards_params, const uint64_t* rescue_params, const void* d_scalars, const void* d_points, size_t count,
+                             void* d_keys);
 /* G2 and the pairing, host-only (no context, no GPU), for the verifier's last step e(A, [tau]_2) * e(-B, [1]_2) == 1 (jf-plonk's verify).
  * G2 points lie on the sextic twist (BN254: y^2 = x^3 + 3/(9+u), BLS12-381: y^2 = x^3 + 4(1+u); Fq2 = Fq[u]/(u^2+1)) and are encoded as
  * x.c0 || x.c1 || y.c0 || y.c1 Montgomery limbs (4Q u64), all zero = infinity; G1 points as x || y (2Q u64), (0, 0) = infinity.  Coordinates
