@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("PLONK_HIP_LIB") or os.path.join(_HERE, "lib", "libplo
 
 PLONK_BN254, PLONK_BLS12_381 = 0, 1
 PLONK_BASES_XY, PLONK_BASES_ARK = 0, 1
+PLONK_BYTES_COMPRESSED, PLONK_BYTES_UNCOMPRESSED = 0, 1
 CURVES = {"bn254": PLONK_BN254, "bls12_381": PLONK_BLS12_381}
 FQ_LIMBS64 = {PLONK_BN254: 4, PLONK_BLS12_381: 6}
 ERR_NAMES = {0: "PLONK_OK", -1: "PLONK_ERR_ARG", -2: "PLONK_ERR_DOMAIN", -3: "PLONK_ERR_HIP",
@@ -134,6 +135,15 @@ SIGNATURES = {
     "plonk_pairing_check": (C.c_int, [C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "plonk_verify_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(VerifyKey), C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
+    "plonk_g1_from_bytes_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "plonk_g1_to_bytes_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t]),
+    "plonk_fr_from_bytes_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "plonk_fr_to_bytes_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "plonk_proofs_from_bytes_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "plonk_codec_first_bad_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_int64)]),
+    "plonk_init_bytes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_size_t, C.c_size_t]),
+    "plonk_g2_from_bytes": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
+    "plonk_g2_to_bytes": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "plonk_init_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t]),
     "plonk_debug_field_op": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "plonk_quotient_evals_dev": (C.c_int, [C.c_void_p, C.POINTER(QuotientInputs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1702,3 +1702,225 @@ extern "C" int plonk_verify_batch_dev(plonk_ctx* ctx, const plonk_verify_key* vk
     return rc;
 }
 
+
+// ---------------------------------------------------------------------------------------------- ark-serialize bytes (codec_kernels.hpp)
+// A G1Affine is x (compressed) or x || y (uncompressed) little-endian with SWFlags in the two top bits of the last byte, an Fr 32 bytes.  The
+// device entry points check every argument, enqueue one launch on the context's stream and return; a bad element is a bit in its status word.
+static size_t g1_wire_bytes(int curve, int encoding) { return (curve == PLONK_BN254 ? 32 : 48) * (encoding == PLONK_BYTES_UNCOMPRESSED ? 2 : 1); }
+static int codec_shape_check(const char* who, int encoding, size_t count, size_t byte_stride, size_t byte_elem, size_t limb_stride, size_t limb_elem) {
+    if (encoding != PLONK_BYTES_COMPRESSED && encoding != PLONK_BYTES_UNCOMPRESSED) return plonk_fail(PLONK_ERR_ARG, "%s: encoding %d", who, encoding);
+    if (byte_stride < byte_elem) return plonk_fail(PLONK_ERR_ARG, "%s: a stride of %zu bytes is shorter than the element (%zu)", who, byte_stride, byte_elem);
+    if (limb_stride < limb_elem) return plonk_fail(PLONK_ERR_ARG, "%s: a stride of %zu u64 is shorter than the element (%zu)", who, limb_stride, limb_elem);
+    if ((uint64_t)count > CODEC_MAX_LANES) return plonk_fail(PLONK_ERR_ARG, "%s: count = %zu exceeds one launch", who, count);
+    return PLONK_OK;
+}
+extern "C" int plonk_g1_from_bytes_dev(plonk_ctx* ctx, const void* d_bytes, size_t in_stride, size_t count, int encoding, int check_subgroup, void* d_out_xy,
+                                       size_t out_stride_u64, void* d_status, size_t status_stride) {
+    CHECK_CTX(ctx);
+    const size_t q2 = ctx->curve == PLONK_BN254 ? 8 : 12;
+    int rc = codec_shape_check("plonk_g1_from_bytes_dev", encoding, count, in_stride, g1_wire_bytes(ctx->curve, encoding), out_stride_u64, q2);
+    if (rc) return rc;
+    if (count == 0) return PLONK_OK;
+    if (!d_bytes) return plonk_fail(PLONK_ERR_ARG, "plonk_g1_from_bytes_dev: d_bytes is null");
+    if (!d_out_xy) return plonk_fail(PLONK_ERR_ARG, "plonk_g1_from_bytes_dev: d_out_xy is null");
+    if (!d_status) return plonk_fail(PLONK_ERR_ARG, "plonk_g1_from_bytes_dev: d_status is null");
+    return codec_g1_decode_run(ctx->curve, d_bytes, d_out_xy, d_status, CodecShape{count, 1, in_stride, 0, out_stride_u64, 0, status_stride}, encoding,
+                               check_subgroup, ctx->stream, "plonk_g1_from_bytes_dev");
+}
+extern "C" int plonk_g1_to_bytes_dev(plonk_ctx* ctx, const void* d_xy, size_t in_stride_u64, size_t count, int encoding, void* d_bytes, size_t out_stride) {
+    CHECK_CTX(ctx);
+    const size_t q2 = ctx->curve == PLONK_BN254 ? 8 : 12;
+    int rc = codec_shape_check("plonk_g1_to_bytes_dev", encoding, count, out_stride, g1_wire_bytes(ctx->curve, encoding), in_stride_u64, q2);
+    if (rc) return rc;
+    if (count == 0) return PLONK_OK;
+    if (!d_xy) return plonk_fail(PLONK_ERR_ARG, "plonk_g1_to_bytes_dev: d_xy is null");
+    if (!d_bytes) return plonk_fail(PLONK_ERR_ARG, "plonk_g1_to_bytes_dev: d_bytes is null");
+    return codec_g1_encode_run(ctx->curve, d_xy, d_bytes, CodecShape{count, 1, in_stride_u64, 0, out_stride, 0, 0}, encoding, ctx->stream, "plonk_g1_to_bytes_dev");
+}
+extern "C" int plonk_fr_from_bytes_dev(plonk_ctx* ctx, const void* d_bytes, size_t in_stride, size_t count, void* d_out, size_t out_stride_u64, void* d_status,
+                                       size_t status_stride) {
+    CHECK_CTX(ctx);
+    int rc = codec_shape_check("plonk_fr_from_bytes_dev", PLONK_BYTES_COMPRESSED, count, in_stride, 32, out_stride_u64, 4);
+    if (rc) return rc;
+    if (count == 0) return PLONK_OK;
+    if (!d_bytes) return plonk_fail(PLONK_ERR_ARG, "plonk_fr_from_bytes_dev: d_bytes is null");
+    if (!d_out) return plonk_fail(PLONK_ERR_ARG, "plonk_fr_from_bytes_dev: d_out is null");
+    if (!d_status) return plonk_fail(PLONK_ERR_ARG, "plonk_fr_from_bytes_dev: d_status is null");
+    return codec_fr_decode_run(ctx->curve, d_bytes, d_out, d_status, CodecShape{count, 1, in_stride, 0, out_stride_u64, 0, status_stride}, ctx->stream,
+                               "plonk_fr_from_bytes_dev");
+}
+extern "C" int plonk_fr_to_bytes_dev(plonk_ctx* ctx, const void* d_fr, size_t in_stride_u64, size_t count, void* d_bytes, size_t out_stride) {
+    CHECK_CTX(ctx);
+    int rc = codec_shape_check("plonk_fr_to_bytes_dev", PLONK_BYTES_COMPRESSED, count, out_stride, 32, in_stride_u64, 4);
+    if (rc) return rc;
+    if (count == 0) return PLONK_OK;
+    if (!d_fr) return plonk_fail(PLONK_ERR_ARG, "plonk_fr_to_bytes_dev: d_fr is null");
+    if (!d_bytes) return plonk_fail(PLONK_ERR_ARG, "plonk_fr_to_bytes_dev: d_bytes is null");
+    return codec_fr_encode_run(ctx->curve, d_fr, d_bytes, CodecShape{count, 1, in_stride_u64, 0, out_stride, 0, 0}, ctx->stream, "plonk_fr_to_bytes_dev");
+}
+extern "C" int plonk_proofs_from_bytes_dev(plonk_ctx* ctx, const void* d_bytes, size_t k, void* d_proofs, void* d_status) {
+    CHECK_CTX(ctx);
+    if (k == 0) return PLONK_OK;
+    if (k > (1u << 22)) return plonk_fail(PLONK_ERR_ARG, "plonk_proofs_from_bytes_dev: %zu proofs (at most 2^22 per call)", k);
+    if (!d_bytes) return plonk_fail(PLONK_ERR_ARG, "plonk_proofs_from_bytes_dev: d_bytes is null");
+    if (!d_proofs) return plonk_fail(PLONK_ERR_ARG, "plonk_proofs_from_bytes_dev: d_proofs is null");
+    if (!d_status) return plonk_fail(PLONK_ERR_ARG, "plonk_proofs_from_bytes_dev: d_status is null");
+    return codec_proofs_run(ctx->curve, d_bytes, k, d_proofs, d_status, ctx->stream, "plonk_proofs_from_bytes_dev");
+}
+// the lowest index with a non-zero status word through the first of the context's two verdict words; synchronises
+static int codec_first_bad(plonk_ctx* ctx, const void* d_status, size_t count, size_t status_stride, int64_t* first, const char* who) {
+    int rc = bad_words(ctx, true);
+    if (!rc) rc = codec_first_bad_run(d_status, count, status_stride, ctx->d_bad, ctx->stream, who);
+    if (rc) return rc;
+    unsigned long long w = ~0ull;
+    HIP_TRY(hipMemcpyAsync(&w, ctx->d_bad, sizeof w, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *first = w == ~0ull ? -1 : (int64_t)w;
+    return PLONK_OK;
+}
+extern "C" int plonk_codec_first_bad_dev(plonk_ctx* ctx, const void* d_status, size_t count, size_t status_stride, int64_t* first) {
+    CHECK_CTX(ctx);
+    if (!first) return plonk_fail(PLONK_ERR_ARG, "plonk_codec_first_bad_dev: first is null");
+    if ((uint64_t)count > CODEC_MAX_LANES) return plonk_fail(PLONK_ERR_ARG, "plonk_codec_first_bad_dev: count = %zu exceeds one launch", count);
+    *first = -1;
+    if (count == 0) return PLONK_OK;
+    if (!d_status) return plonk_fail(PLONK_ERR_ARG, "plonk_codec_first_bad_dev: d_status is null");
+    return codec_first_bad(ctx, d_status, count, status_stride, first, "plonk_codec_first_bad_dev");
+}
+extern "C" int plonk_init_bytes(plonk_ctx* ctx, const void* bytes, size_t n_bases, int encoding, int check_subgroup, size_t domain_size, size_t quot_domain_size) {
+    CHECK_CTX(ctx);
+    if (n_bases && !bytes) return plonk_fail(PLONK_ERR_ARG, "plonk_init_bytes: null bases");
+    const size_t nb = g1_wire_bytes(ctx->curve, encoding), ab = aff_bytes(ctx->curve);
+    int rc = codec_shape_check("plonk_init_bytes", encoding, n_bases, nb, nb, ab / 8, ab / 8);
+    if (!rc) rc = set_domains(ctx, domain_size, quot_domain_size);
+    if (rc) return rc;
+    if (ctx->d_bases) (void)hipFree(ctx->d_bases);
+    ctx->d_bases = nullptr; ctx->n_bases = 0; ctx->msm_table = MsmTable();
+    if (!n_bases) return PLONK_OK;
+    struct Staging {            // bytes, status words and the decoded (x, y): released on every exit, after the stream has finished with them
+        void* bytes = nullptr; void* status = nullptr; void* xy = nullptr; hipStream_t s;
+        void drop_inputs() { (void)hipStreamSynchronize(s); if (bytes) (void)hipFree(bytes); if (status) (void)hipFree(status); bytes = status = nullptr; }
+        ~Staging() { drop_inputs(); if (xy) (void)hipFree(xy); }
+    } d;
+    d.s = ctx->stream;
+    HIP_TRY(hipMalloc(&d.bytes, n_bases * nb));
+    HIP_TRY(hipMalloc(&d.status, n_bases * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(&d.xy, n_bases * ab));
+    HIP_TRY(hipMemcpyAsync(d.bytes, bytes, n_bases * nb, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(d.status, 0, n_bases * sizeof(uint32_t), ctx->stream));
+    if ((rc = codec_g1_decode_run(ctx->curve, d.bytes, d.xy, d.status, CodecShape{n_bases, 1, nb, 0, ab / 8, 0, 1}, encoding, check_subgroup, ctx->stream,
+                                  "plonk_init_bytes")))
+        return rc;
+    int64_t first = -1;
+    if ((rc = codec_first_bad(ctx, d.status, n_bases, 1, &first, "plonk_init_bytes"))) return rc;
+    if (first >= 0) {
+        uint32_t st = 0;
+        HIP_TRY(hipMemcpy(&st, (const uint32_t*)d.status + first, sizeof st, hipMemcpyDeviceToHost));
+        return plonk_fail(PLONK_ERR_ARG, "plonk_init_bytes: base %lld does not decode (status %u:%s%s%s)", (long long)first, st,
+                          st & 1 ? " no point has this x, or the pair is off the curve" : "", st & 2 ? " outside the r-subgroup" : "",
+                          st & 8 ? " non-canonical encoding" : "");
+    }
+    d.drop_inputs();
+    return install_bases(ctx, d.xy, n_bases, "plonk_init_bytes");
+}
+
+// ---- G2 as bytes, host only: x.c0 || x.c1 (|| y.c0 || y.c1) little-endian, flags in the last byte.  "y is the larger" compares c1 first and c0 on a
+// tie (ark-ff 0.3's ordering of a quadratic extension as far as the public sources show: DESIGN.md §5).
+template <int N> static bool fq_sqrt(const Fp<N>& a, Fp<N>& r, const FpParams<N>& P) {
+    r = fp_sqrt_3mod4(a, P);
+    return fp_eq(fp_sqr(r, P), a);
+}
+// Fq2 = Fq[u]/(u^2 + 1), q = 3 (mod 4): alpha = sqrt(norm), x0 = sqrt((c0 +- alpha) / 2), x1 = c1 / (2 x0); checked by squaring
+template <int N> static bool fq2_sqrt(const pairing::Fq2<N>& a, pairing::Fq2<N>& r, const FpParams<N>& P) {
+    Fp<N> s;
+    if (fp_is_zero(a.c1)) {                    // a in Fq: sqrt(c0), or sqrt(-c0) u (-1 is a non-residue: one of the two exists)
+        if (fq_sqrt(a.c0, s, P)) { r = {s, fp_zero<N>()}; return true; }
+        if (fq_sqrt(fp_neg(a.c0, P), s, P)) { r = {fp_zero<N>(), s}; return true; }
+        return false;
+    }
+    Fp<N> alpha;
+    if (!fq_sqrt(fp_add(fp_sqr(a.c0, P), fp_sqr(a.c1, P), P), alpha, P)) return false;
+    const Fp<N> one = fp_one(P), half = fp_inv(fp_add(one, one, P), P);
+    Fp<N> x0;
+    if (!fq_sqrt(fp_mul(fp_add(a.c0, alpha, P), half, P), x0, P) && !fq_sqrt(fp_mul(fp_sub(a.c0, alpha, P), half, P), x0, P)) return false;
+    if (fp_is_zero(x0)) return false;
+    r = {x0, fp_mul(a.c1, fp_inv(fp_add(x0, x0, P), P), P)};
+    return pairing::f2_eq(pairing::f2_mul(r, r, P), a);
+}
+template <int N> static int cmp_canon(const Fp<N>& a_mont, const Fp<N>& b_mont, const FpParams<N>& P) {
+    const Fp<N> a = fp_from_mont(a_mont, P), b = fp_from_mont(b_mont, P);
+    for (int j = N - 1; j >= 0; j--)
+        if (a.l[j] != b.l[j]) return a.l[j] < b.l[j] ? -1 : 1;
+    return 0;
+}
+template <int N> static bool fq2_y_is_larger(const pairing::Fq2<N>& y, const FpParams<N>& P) {
+    const pairing::Fq2<N> ny = pairing::f2_neg(y, P);
+    const int c = cmp_canon(y.c1, ny.c1, P);
+    return c ? c > 0 : cmp_canon(y.c0, ny.c0, P) > 0;
+}
+template <int N> static int g2_from_bytes_t(const uint8_t* in, int encoding, uint64_t* out, int* status) {
+    const pairing::Curve<N>& C = pairing::curve<N>();
+    const FpParams<N>& P = *C.P;
+    const int nc = encoding == PLONK_BYTES_UNCOMPRESSED ? 4 : 2;
+    Fp<N> c[4] = {fp_zero<N>(), fp_zero<N>(), fp_zero<N>(), fp_zero<N>()};
+    for (int i = 0; i < nc; i++)
+        for (int j = 0; j < 4 * N; j++) c[i].l[j >> 2] |= (uint32_t)in[4 * N * i + j] << (8 * (j & 3));
+    const uint32_t flags = c[nc - 1].l[N - 1] >> 30;
+    c[nc - 1].l[N - 1] &= 0x3FFFFFFFu;
+    const bool sign = flags & 2, inf = flags & 1;
+    int st = 0;
+    pairing::G2<N> q = {pairing::f2_zero<N>(), pairing::f2_zero<N>(), true};
+    bool zero = true, canon = true;
+    for (int i = 0; i < nc; i++) {
+        zero = zero && fp_is_zero(c[i]);
+        bool lt = false;
+        for (int j = N - 1; j >= 0; j--)
+            if (c[i].l[j] != P.p[j]) { lt = c[i].l[j] < P.p[j]; break; }
+        canon = canon && lt;
+    }
+    if ((sign && inf) || (sign && nc == 4) || (inf && !zero) || (!inf && !canon)) st = 8;
+    else if (!inf) {
+        const pairing::Fq2<N> x = {fp_to_mont(c[0], P), fp_to_mont(c[1], P)};
+        const pairing::Fq2<N> rhs = pairing::f2_add(pairing::f2_mul(pairing::f2_mul(x, x, P), x, P), C.b2, P);
+        pairing::Fq2<N> y = {fp_to_mont(c[2], P), fp_to_mont(c[3], P)};
+        if (nc == 4) {
+            if (!pairing::f2_eq(pairing::f2_mul(y, y, P), rhs)) st = 1;
+        } else if (!fq2_sqrt(rhs, y, P)) st = 1;
+        else if (fq2_y_is_larger(y, P) != sign) y = pairing::f2_neg(y, P);
+        if (!st) {
+            q = {x, y, false};
+            if (!pairing::g2_check(q, C)) st = 2;
+        }
+    }
+    if (st) q.inf = true;
+    g2_store<N>(q, out);
+    *status = st;
+    return PLONK_OK;
+}
+template <int N> static int g2_to_bytes_t(const uint64_t* in, int encoding, uint8_t* out) {
+    const pairing::Curve<N>& C = pairing::curve<N>();
+    const FpParams<N>& P = *C.P;
+    pairing::G2<N> q;
+    int rc = g2_load<N>(in, q, "plonk_g2_to_bytes");
+    if (rc) return rc;
+    const int nc = encoding == PLONK_BYTES_UNCOMPRESSED ? 4 : 2;
+    const Fp<N> c[4] = {fp_from_mont(q.x.c0, P), fp_from_mont(q.x.c1, P), fp_from_mont(q.y.c0, P), fp_from_mont(q.y.c1, P)};
+    for (int i = 0; i < nc; i++)
+        for (int j = 0; j < 4 * N; j++) out[4 * N * i + j] = q.inf ? 0 : (uint8_t)(c[i].l[j >> 2] >> (8 * (j & 3)));
+    out[4 * N * nc - 1] |= q.inf ? 0x40 : (nc == 2 && fq2_y_is_larger(q.y, P) ? 0x80 : 0);
+    return PLONK_OK;
+}
+extern "C" int plonk_g2_from_bytes(int curve, const uint8_t* in, int encoding, uint64_t* out, int* status) {
+    if (!in || !out || !status) return plonk_fail(PLONK_ERR_ARG, "plonk_g2_from_bytes: null");
+    if (encoding != PLONK_BYTES_COMPRESSED && encoding != PLONK_BYTES_UNCOMPRESSED) return plonk_fail(PLONK_ERR_ARG, "plonk_g2_from_bytes: encoding %d", encoding);
+    if (curve == PLONK_BN254) return g2_from_bytes_t<8>(in, encoding, out, status);
+    if (curve == PLONK_BLS12_381) return g2_from_bytes_t<12>(in, encoding, out, status);
+    return plonk_fail(PLONK_ERR_ARG, "plonk_g2_from_bytes: unknown curve %d", curve);
+}
+extern "C" int plonk_g2_to_bytes(int curve, const uint64_t* in, int encoding, uint8_t* out) {
+    if (!in || !out) return plonk_fail(PLONK_ERR_ARG, "plonk_g2_to_bytes: null");
+    if (encoding != PLONK_BYTES_COMPRESSED && encoding != PLONK_BYTES_UNCOMPRESSED) return plonk_fail(PLONK_ERR_ARG, "plonk_g2_to_bytes: encoding %d", encoding);
+    if (curve == PLONK_BN254) return g2_to_bytes_t<8>(in, encoding, out);
+    if (curve == PLONK_BLS12_381) return g2_to_bytes_t<12>(in, encoding, out);
+    return plonk_fail(PLONK_ERR_ARG, "plonk_g2_to_bytes: unknown curve %d", curve);
+}

@@ -233,6 +233,23 @@ size_t verify_batch_scratch_bytes(size_t k);
 int verify_batch_run(int curve, const uint8_t* strobe, const uint32_t* strobe_pos3, size_t log_n, size_t num_inputs, const uint64_t* k_mont,
                      const Fr& omega, const Fr& n_fr, const void* d_proofs, const void* d_vk_pts, const void* d_pub, const void* d_rho, size_t k,
                      void* d_out, void* d_status, void* d_debug, void* scratch, hipStream_t stream);
+// ark-serialize bytes <-> Montgomery limbs (codec_kernels.hpp, built in synth.hip).  Element i = o * inner + j of a launch sits at
+// base + o * stride + j * inner_stride on both sides (bytes on the byte side, u64 on the limb side) and reports into status[o * status_stride];
+// base pointers already carry the offset of element 0.  Status words are OR-ed into, never cleared, except by codec_proofs_run.  Enqueued only.
+struct CodecShape {
+    uint64_t count;                              // elements = lanes
+    uint32_t inner;                              // elements per record, >= 1
+    uint64_t in_stride, in_inner, out_stride, out_inner, status_stride;
+};
+constexpr uint64_t CODEC_MAX_LANES = 0x7FFFFFFFull * 128;          // what one launch holds
+int codec_g1_decode_run(int curve, const void* d_bytes, void* d_out, void* d_status, const CodecShape& s, int uncompressed, int check_subgroup,
+                        hipStream_t stream, const char* who);
+int codec_g1_encode_run(int curve, const void* d_xy, void* d_bytes, const CodecShape& s, int uncompressed, hipStream_t stream, const char* who);
+int codec_fr_decode_run(int curve, const void* d_bytes, void* d_out, void* d_status, const CodecShape& s, hipStream_t stream, const char* who);
+int codec_fr_encode_run(int curve, const void* d_fr, void* d_bytes, const CodecShape& s, hipStream_t stream, const char* who);
+size_t codec_proof_bytes(int curve);             // transcript.serialize_proof's length: 768 / 976
+int codec_proofs_run(int curve, const void* d_bytes, size_t k, void* d_proofs, void* d_status, hipStream_t stream, const char* who);
+int codec_first_bad_run(const void* d_status, size_t count, size_t status_stride, unsigned long long* d_first, hipStream_t stream, const char* who);
 size_t circuit_permutation_scratch_bytes(size_t n, size_t num_vars);
 int circuit_permutation_run(int curve, const uint32_t* wire_vars, size_t n, size_t num_vars, const uint64_t* k_mont, const Fr& omega_n,
                             Fr* id_perm, uint64_t* perm_idx, Fr* sigma, void* scratch, hipStream_t stream);

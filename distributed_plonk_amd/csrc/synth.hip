@@ -372,3 +372,5 @@ int synth_circuit_dev(int curve, uint64_t seed, size_t n, size_t num_inputs, con
 // ---------------------------------------------------------------------------------------------- batched proof verification
 // the per-proof work of jf-plonk's verify / batch_verify up to the pairing: kernels and launcher in their own header
 #include "verify_kernels.hpp"
+// what a prover, a ceremony and a key file hand over is bytes: ark-serialize's G1 and Fr encodings read and written on the device
+#include "codec_kernels.hpp"

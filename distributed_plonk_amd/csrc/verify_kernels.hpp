@@ -295,6 +295,8 @@ __global__ void __launch_bounds__(vfy::LANES) verify_scalars_kernel(const vfy::P
 }
 
 // ------------------------------------------------------------------------------------------------ kernel 2: r-subgroup of G1 (BLS12-381)
+// (the loop below has a copy, codec::g1_times_r_is_inf in codec_kernels.hpp, kept apart so that this kernel's machine code stays what the
+// counters of profiles/ were collected from: a change to the one belongs in the other too)
 template <int NQ>
 __global__ void __launch_bounds__(128) verify_subgroup_kernel(const uint32_t* __restrict__ proofs, uint32_t k, uint32_t* __restrict__ status,
                                                                const FpParams<8> R, const FpParams<NQ> Q) {

@@ -118,6 +118,23 @@ class OpenKey:
         h = g2_generator(curve)
         return cls(curve, g1_generator(curve), h, g2_mul(curve, _fr.FIELDS[curve].to_limbs(tau % _fr.FIELDS[curve].p), h))
 
+    @classmethod
+    def from_bytes(cls, curve: str, g: bytes, h: bytes, beta_h: bytes) -> "OpenKey":
+        """The key from its three serialized elements (ark-serialize 0.3, compressed or uncompressed by their length): g a G1Affine, h and
+        beta_h G2Affine (`plonk_g2_from_bytes`).  g has to be the generator, so it is compared as bytes; a G2 element that does not decode
+        raises ValueError naming its status."""
+        from . import codec
+        xy = g1_generator(curve)
+        if bytes(g) not in (codec.g1_encode_host(curve, xy, "compressed"), codec.g1_encode_host(curve, xy, "uncompressed")):
+            raise ValueError("OpenKey: g must be the G1 generator the prover's commitments and the device verifier use")
+        pts = []
+        for name, blob in (("h", h), ("beta_h", beta_h)):
+            pt, st = codec.g2_from_bytes(curve, blob)
+            if st:
+                raise ValueError(f"OpenKey: {name} does not decode: {codec.status_text(st)}")
+            pts.append(pt)
+        return cls(curve, xy, pts[0], pts[1])
+
 
 def _jac(curve: str, xy: np.ndarray) -> np.ndarray:
     n = _q64(curve)
@@ -173,18 +190,32 @@ def device_verify(worker, vk: dict, public_inputs_list, proofs, rho: np.ndarray,
     num_inputs = pis[0].shape[0] if K else 0
     if any(p.shape[0] != num_inputs for p in pis):
         raise ValueError("every proof of a batch needs the same number of public inputs")
+    recs = np.stack([proof_record(curve, p) for p in proofs]) if K else np.zeros((0, 2 * n64 * NPTS + 4 * NEVALS), np.uint64)
+    pub = np.concatenate(pis) if num_inputs else np.zeros((1, 4), np.uint64)
+    bufs = []
+    try:
+        for arr in (recs, pub):
+            bufs.append(worker.alloc(max(arr.nbytes, 8)))
+            bufs[-1].upload(arr)
+        return device_verify_records(worker, vk, num_inputs, K, bufs[0].ptr, bufs[1].ptr, rho, debug)
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def device_verify_records(worker, vk: dict, num_inputs: int, K: int, d_recs: int, d_pub: int, rho: np.ndarray, debug: bool = False):
+    """What device_verify does after the upload: K proof records and K x num_inputs public inputs already on the device (pointers) ->
+    (points, status, debug) as device_verify returns them."""
+    curve = worker.curve_name
+    n64 = _q64(curve)
     if len(vk["selector_comms"]) != 13 or len(vk["sigma_comms"]) != 5:
         raise ValueError("verifying key shape")
     key = _vk_state(curve, vk, num_inputs)
     comms = np.concatenate([_point_xy(curve, c) for c in list(vk["selector_comms"]) + list(vk["sigma_comms"])])
-    recs = np.stack([proof_record(curve, p) for p in proofs]) if K else np.zeros((0, 2 * n64 * NPTS + 4 * NEVALS), np.uint64)
     bufs = []
     alloc = lambda nbytes: bufs.append(worker.alloc(max(nbytes, 8))) or bufs[-1]
     try:
         d_comms = alloc(comms.nbytes).upload(comms)
-        d_recs = alloc(recs.nbytes).upload(recs)
-        pub = np.concatenate(pis) if num_inputs else np.zeros((1, 4), np.uint64)
-        d_pub = alloc(pub.nbytes).upload(pub)
         d_rho = alloc(rho.nbytes).upload(np.ascontiguousarray(rho, dtype=np.uint64))
         d_out = alloc(K * 2 * 2 * n64 * 8)
         d_status = alloc(K * 4)
@@ -192,7 +223,7 @@ def device_verify(worker, vk: dict, public_inputs_list, proofs, rho: np.ndarray,
         if debug:
             worker.memset_dev(d_dbg.ptr, 0, K * 9 * 32)
         key.d_comms = d_comms.ptr
-        _ffi.check(_lib().plonk_verify_batch_dev(worker.ctx, C.byref(key), K, d_recs.ptr, d_pub.ptr if num_inputs else None, d_rho.ptr, d_out.ptr,
+        _ffi.check(_lib().plonk_verify_batch_dev(worker.ctx, C.byref(key), K, d_recs, d_pub if num_inputs else None, d_rho.ptr, d_out.ptr,
                                                  d_status.ptr, d_dbg.ptr if debug else None))
         pts = d_out.download((K, 2, 2 * n64))
         status = d_status.download((K,), dtype=np.uint32)
@@ -218,7 +249,17 @@ def batch_verify(worker, vk: dict, open_key: OpenKey, public_inputs_list, proofs
     K = len(proofs)
     rho = _rhos(curve, K, seed) if _rho is None else _rho
     pts, status, _ = device_verify(worker, vk, public_inputs_list, proofs, rho)
-    verdict = [False] * K
+    verdict, checks = _bisect(worker, open_key, pts, [i for i in range(K) if status[i] == 0])
+    if stats is not None:
+        stats["pairing_checks"] = checks
+        stats["status"] = [int(s) for s in status]
+    return verdict
+
+
+def _bisect(worker, open_key: OpenKey, pts: np.ndarray, eligible: list):
+    """(verdicts, pairing checks): one folded pairing check over the eligible proofs, halved while it fails."""
+    curve = worker.curve_name
+    verdict = [False] * pts.shape[0]
     checks = [0]
 
     def holds(idx):
@@ -237,10 +278,54 @@ def batch_verify(worker, vk: dict, open_key: OpenKey, public_inputs_list, proofs
             bisect(idx[:len(idx) // 2])
             bisect(idx[len(idx) // 2:])
 
-    bisect([i for i in range(K) if status[i] == 0])
+    bisect(list(eligible))
+    return verdict, checks[0]
+
+
+def batch_verify_bytes(worker, vk: dict, open_key: OpenKey, public_inputs_bytes, proof_blobs, seed: Optional[int] = None,
+                       stats: Optional[dict] = None) -> list:
+    """batch_verify on what a prover sends: proof_blobs[i] a serialized `Proof` (transcript.serialize_proof), public_inputs_bytes[i] its
+    public inputs, 32 bytes each.  Proofs and inputs are decoded on the device (codec.proofs_from_bytes_dev, plonk_fr_from_bytes_dev) and the
+    records go to plonk_verify_batch_dev where they are.  A proof that does not decode is rejected without touching the others; `stats`
+    receives "decode_status" beside batch_verify's "pairing_checks" and "status"."""
+    from . import codec
+    curve = worker.curve_name
+    if open_key.curve != curve:
+        raise ValueError("open key and worker are on different curves")
+    K = len(proof_blobs)
+    if len(public_inputs_bytes) != K:
+        raise ValueError("one public-input blob per proof")
+    pubs = [bytes(p) for p in public_inputs_bytes]
+    if any(len(p) % 32 or len(p) != len(pubs[0]) for p in pubs):
+        raise ValueError("every proof of a batch needs the same number of public inputs, 32 bytes each")
+    num_inputs = len(pubs[0]) // 32 if K else 0
+    if K == 0:
+        if stats is not None:
+            stats.update(pairing_checks=0, status=[], decode_status=[])
+        return []
+    rho = _rhos(curve, K, seed)
+    d_recs, decode = codec.proofs_from_bytes_dev(worker, proof_blobs)
+    bufs = [d_recs]                              # everything allocated below is freed on every exit
+    alloc = lambda nbytes: bufs.append(worker.alloc(nbytes)) or bufs[-1]
+    try:
+        d_pub = None
+        if num_inputs:
+            raw = np.frombuffer(b"".join(pubs), dtype=np.uint8)
+            d_raw = alloc(raw.nbytes).upload(raw)
+            d_pub = alloc(K * num_inputs * 32)
+            d_st = alloc(K * num_inputs * 4)
+            worker.memset_dev(d_st.ptr, 0, K * num_inputs * 4)
+            worker.fr_from_bytes_dev(d_raw.ptr, 32, K * num_inputs, d_pub.ptr, 4, d_st.ptr, 1)
+            decode = decode | np.bitwise_or.reduce(d_st.download((K, num_inputs), dtype=np.uint32), axis=1)
+        pts, status, _ = device_verify_records(worker, vk, num_inputs, K, d_recs.ptr, d_pub.ptr if d_pub else 0, rho)
+    finally:
+        for b in bufs:
+            b.free()
+    verdict, checks = _bisect(worker, open_key, pts, [i for i in range(K) if decode[i] == 0 and status[i] == 0])
     if stats is not None:
-        stats["pairing_checks"] = checks[0]
+        stats["pairing_checks"] = checks
         stats["status"] = [int(s) for s in status]
+        stats["decode_status"] = [int(s) for s in decode]
     return verdict
 
 

@@ -518,6 +518,45 @@ class PlonkWorker:
         r = None if rescue_params is None else _u64(rescue_params)
         check(self.lib.plonk_edwards_dh_key_dev(self.ctx, _ptr(e), _ptr(r), d_scalars or None, d_points or None, count, d_keys or None))
 
+    # ------------------------------------------------------------------ ark-serialize bytes <-> limbs on the device (codec.py)
+    def g1_from_bytes_dev(self, d_bytes: int, in_stride: int, count: int, encoding: int, check_subgroup: bool, d_out_xy: int, out_stride_u64: int,
+                          d_status: int, status_stride: int = 1):
+        """Element i at d_bytes + i * in_stride -> x || y at d_out_xy + 8 * i * out_stride_u64; its status bits are OR-ed into the u32 at
+        d_status + 4 * i * status_stride, which the caller cleared (plonk_g1_from_bytes_dev).  Enqueued, not synchronised."""
+        check(self.lib.plonk_g1_from_bytes_dev(self.ctx, d_bytes or None, in_stride, count, encoding, 1 if check_subgroup else 0, d_out_xy or None,
+                                               out_stride_u64, d_status or None, status_stride))
+
+    def g1_to_bytes_dev(self, d_xy: int, in_stride_u64: int, count: int, encoding: int, d_bytes: int, out_stride: int):
+        """The inverse (plonk_g1_to_bytes_dev).  Enqueued, not synchronised."""
+        check(self.lib.plonk_g1_to_bytes_dev(self.ctx, d_xy or None, in_stride_u64, count, encoding, d_bytes or None, out_stride))
+
+    def fr_from_bytes_dev(self, d_bytes: int, in_stride: int, count: int, d_out: int, out_stride_u64: int, d_status: int, status_stride: int = 1):
+        """32 bytes little-endian -> Fr Montgomery; status 8 and 0 for a value >= r (plonk_fr_from_bytes_dev).  Enqueued, not synchronised."""
+        check(self.lib.plonk_fr_from_bytes_dev(self.ctx, d_bytes or None, in_stride, count, d_out or None, out_stride_u64, d_status or None, status_stride))
+
+    def fr_to_bytes_dev(self, d_fr: int, in_stride_u64: int, count: int, d_bytes: int, out_stride: int):
+        check(self.lib.plonk_fr_to_bytes_dev(self.ctx, d_fr or None, in_stride_u64, count, d_bytes or None, out_stride))
+
+    def proofs_from_bytes_dev(self, d_bytes: int, k: int, d_proofs: int, d_status: int):
+        """k serialized proofs -> k records of plonk_verify_batch_dev and k status words (plonk_proofs_from_bytes_dev).  Enqueued, not synchronised."""
+        check(self.lib.plonk_proofs_from_bytes_dev(self.ctx, d_bytes or None, k, d_proofs or None, d_status or None))
+
+    def codec_first_bad_dev(self, d_status: int, count: int, status_stride: int = 1) -> int:
+        """The lowest index with a non-zero status word, -1 when there is none (plonk_codec_first_bad_dev).  Synchronises."""
+        first = C.c_int64(-1)
+        check(self.lib.plonk_codec_first_bad_dev(self.ctx, d_status or None, count, status_stride, C.byref(first)))
+        return first.value
+
+    def init_bytes(self, data, n_bases: int, domain_size: int, quot_domain_size: int, encoding: str = "compressed", check_subgroup: bool = True):
+        """`init` for an SRS of n_bases serialized points back to back (plonk_init_bytes): decoded on the device.  One bad point raises, naming
+        its index and status, and leaves the worker without bases."""
+        from . import codec
+        b = codec._u8(data)                        # a view of the caller's bytes, not a copy: an SRS of 2^24 points is 512 MiB
+        enc = codec.ENCODINGS[encoding]
+        if b.size != n_bases * codec.g1_nbytes(self.curve_name, encoding):
+            raise ValueError(f"init_bytes: {b.size} bytes for {n_bases} {encoding} points")
+        check(self.lib.plonk_init_bytes(self.ctx, _ptr(b) if n_bases else None, n_bases, enc, 1 if check_subgroup else 0, domain_size, quot_domain_size))
+
     def circuit_scatter_inputs_dev(self, d_input_vars: int, num_inputs: int, d_inputs: int, d_witness: int, num_vars: int):
         """witness[input_vars[k]] = inputs[k] on the device (plonk_circuit_scatter_inputs_dev); d_input_vars: u32.  Synchronises."""
         check(self.lib.plonk_circuit_scatter_inputs_dev(self.ctx, d_input_vars or None, num_inputs, d_inputs or None, d_witness or None, num_vars))

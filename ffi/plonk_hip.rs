@@ -21,6 +21,8 @@ pub const PLONK_BN254: c_int = 0;
 pub const PLONK_BLS12_381: c_int = 1;
 pub const PLONK_BASES_XY: c_int = 0;
 pub const PLONK_BASES_ARK: c_int = 1;
+pub const PLONK_BYTES_COMPRESSED: c_int = 0;
+pub const PLONK_BYTES_UNCOMPRESSED: c_int = 1;
 pub const PLONK_OK: c_int = 0;
 pub const PLONK_ERR_ARG: c_int = -1;
 pub const PLONK_ERR_DOMAIN: c_int = -2;
@@ -189,6 +191,15 @@ extern "C" {
     pub fn plonk_pairing_check(curve: c_int, k: usize, g1_xy: *const u64, g2_xy: *const u64, is_one: *mut c_int) -> c_int;
     pub fn plonk_verify_batch_dev(ctx: *mut plonk_ctx, vk: *const plonk_verify_key, k: usize, d_proofs: *const c_void, d_pub_inputs: *const c_void,
                                   d_rho: *const c_void, d_out_points: *mut c_void, d_status: *mut c_void, d_debug: *mut c_void) -> c_int;
+    pub fn plonk_g1_from_bytes_dev(ctx: *mut plonk_ctx, d_bytes: *const c_void, in_stride: usize, count: usize, encoding: c_int, check_subgroup: c_int, d_out_xy: *mut c_void, out_stride_u64: usize, d_status: *mut c_void, status_stride: usize) -> c_int;
+    pub fn plonk_g1_to_bytes_dev(ctx: *mut plonk_ctx, d_xy: *const c_void, in_stride_u64: usize, count: usize, encoding: c_int, d_bytes: *mut c_void, out_stride: usize) -> c_int;
+    pub fn plonk_fr_from_bytes_dev(ctx: *mut plonk_ctx, d_bytes: *const c_void, in_stride: usize, count: usize, d_out: *mut c_void, out_stride_u64: usize, d_status: *mut c_void, status_stride: usize) -> c_int;
+    pub fn plonk_fr_to_bytes_dev(ctx: *mut plonk_ctx, d_fr: *const c_void, in_stride_u64: usize, count: usize, d_bytes: *mut c_void, out_stride: usize) -> c_int;
+    pub fn plonk_proofs_from_bytes_dev(ctx: *mut plonk_ctx, d_bytes: *const c_void, k: usize, d_proofs: *mut c_void, d_status: *mut c_void) -> c_int;
+    pub fn plonk_codec_first_bad_dev(ctx: *mut plonk_ctx, d_status: *const c_void, count: usize, status_stride: usize, first: *mut i64) -> c_int;
+    pub fn plonk_init_bytes(ctx: *mut plonk_ctx, bytes: *const c_void, n_bases: usize, encoding: c_int, check_subgroup: c_int, domain_size: usize, quot_domain_size: usize) -> c_int;
+    pub fn plonk_g2_from_bytes(curve: c_int, input: *const u8, encoding: c_int, out: *mut u64, status: *mut c_int) -> c_int;
+    pub fn plonk_g2_to_bytes(curve: c_int, input: *const u64, encoding: c_int, out: *mut u8) -> c_int;
     pub fn plonk_init_dev(ctx: *mut plonk_ctx, d_bases_xy: *const c_void, n_bases: usize, domain_size: usize, quot_domain_size: usize) -> c_int;
     pub fn plonk_debug_field_op(ctx: *mut plonk_ctx, field: c_int, op: c_int, a: *const u64, b: *const u64, out: *mut u64, n: usize) -> c_int;
     pub fn plonk_set_option(ctx: *mut plonk_ctx, key: *const c_char, value: i64) -> c_int;

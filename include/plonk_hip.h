@@ -522,6 +522,48 @@ typedef struct plonk_verify_key {
 } plonk_verify_key;
 int plonk_verify_batch_dev(plonk_ctx* ctx, const plonk_verify_key* vk, size_t k, const void* d_proofs, const void* d_pub_inputs, const void* d_rho,
                            void* d_out_points, void* d_status, void* d_debug);
+/* ark-serialize 0.3 bytes <-> Montgomery limbs (`to_bytes!` of the reference; csrc/codec_kernels.hpp), one lane per element.
+ * A G1Affine is, compressed, its x coordinate little-endian (32 B BN254 / 48 B BLS12-381) with two flags in the top bits of the last byte:
+ * 0x80 "y is the larger of {y, -y} as integers", 0x40 infinity; uncompressed, x then y (64 B / 96 B), the last byte of y carrying only 0x40.
+ * An Fr is 32 bytes little-endian, canonical.  Decoding a compressed point is one Fq power, y = (x^3 + b)^((q+1)/4) (q = 3 mod 4 on both
+ * curves), and one squaring to test it.  Element i is read at base + i * stride and written at base + i * stride on the other side (strides
+ * in BYTES on the byte side — any value >= the element, no alignment needed — and in u64 on the limb side); what lies between elements is
+ * left untouched.  Points come out as x || y (2Q u64, the PLONK_BASES_XY / proof-record form, (0, 0) = infinity).
+ * A bad element is never an error code: its bits are OR-ed (atomically) into the u32 at d_status + i * status_stride (in u32; 0 lets all
+ * elements share one word) and (0, 0) — for an Fr, 0 — is written.  The caller clears the status words first.
+ *     1   no point has this x, or the uncompressed pair is off the curve
+ *     2   outside the r-subgroup (only with check_subgroup != 0 and only on BLS12-381: [r] P != O; BN254's G1 has cofactor 1)
+ *     8   non-canonical: a coordinate >= q or a scalar >= r, both flags set, the infinity flag with a non-zero coordinate (stricter than
+ *         ark-serialize, which as far as the public sources show ignores those bytes: DESIGN.md §5), the sign flag in an uncompressed element
+ *     16  (plonk_proofs_from_bytes_dev) a Vec length prefix of the serialized Proof differs from 5, 5, 5, 4
+ * 1, 2 and 8 mean what they mean in plonk_verify_batch_dev's status.  The *_dev entry points are ordered on the context's stream and
+ * return once enqueued; count = 0 is a no-op; a NULL pointer with count > 0, a stride shorter than the element, an unknown encoding and a
+ * count beyond one launch are PLONK_ERR_ARG naming the entry point. */
+enum { PLONK_BYTES_COMPRESSED = 0, PLONK_BYTES_UNCOMPRESSED = 1 };
+int plonk_g1_from_bytes_dev(plonk_ctx* ctx, const void* d_bytes, size_t in_stride, size_t count, int encoding, int check_subgroup, void* d_out_xy,
+                            size_t out_stride_u64, void* d_status, size_t status_stride);
+int plonk_g1_to_bytes_dev(plonk_ctx* ctx, const void* d_xy, size_t in_stride_u64, size_t count, int encoding, void* d_bytes, size_t out_stride);
+int plonk_fr_from_bytes_dev(plonk_ctx* ctx, const void* d_bytes, size_t in_stride, size_t count, void* d_out, size_t out_stride_u64, void* d_status,
+                            size_t status_stride);
+int plonk_fr_to_bytes_dev(plonk_ctx* ctx, const void* d_fr, size_t in_stride_u64, size_t count, void* d_bytes, size_t out_stride);
+/* k serialized `Proof`s (768 B each on BN254, 976 B on BLS12-381: 13 compressed points and 10 Fr behind four u64 Vec lengths, the layout of
+ * transcript.serialize_proof — not pinned by a reference-generated proof) -> k records of plonk_verify_batch_dev in d_proofs
+ * and one status word per proof in d_status (cleared here).  Five launches, seven on BLS12-381: two point decodes (each followed there by
+ * the r-subgroup check as a launch of its own), two scalar decodes, the length prefixes.  A proof with a non-zero status must not be handed
+ * to the verifier as if it were sound: its bad elements are zeros. */
+int plonk_proofs_from_bytes_dev(plonk_ctx* ctx, const void* d_bytes, size_t k, void* d_proofs, void* d_status);
+/* *first = the lowest i < count with a non-zero u32 at d_status + i * status_stride, -1 when there is none.  Synchronises. */
+int plonk_codec_first_bad_dev(plonk_ctx* ctx, const void* d_status, size_t count, size_t status_stride, int64_t* first);
+/* plonk_init for an SRS given as bytes (HOST memory, n_bases elements back to back): upload, decode into a temporary, plonk_init_dev.  One
+ * bad point makes an SRS unusable: PLONK_ERR_ARG naming the first bad index and its status, and the context is left without bases. */
+int plonk_init_bytes(plonk_ctx* ctx, const void* bytes, size_t n_bases, int encoding, int check_subgroup, size_t domain_size, size_t quot_domain_size);
+/* G2 points as bytes, host only (the two G2 points of a verifier's key): x.c0 || x.c1 (|| y.c0 || y.c1) little-endian, Q bytes x 8 each, the
+ * flags in the last byte.  "Larger y" compares c1 first and c0 on a tie.  The root in Fq2 = Fq[u]/(u^2 + 1) is taken through the norm:
+ * alpha = sqrt(c0^2 + c1^2), x0 = sqrt((c0 +- alpha) / 2), x1 = c1 / (2 x0), and checked by squaring.  *status: the bits above, 2 from
+ * plonk_g2_check's test, on both curves; out: 4Q u64 as for plonk_g2_mul, zeros unless *status = 0.  plonk_g2_to_bytes wants a point
+ * plonk_g2_mul would accept (PLONK_ERR_ARG otherwise). */
+int plonk_g2_from_bytes(int curve, const uint8_t* in, int encoding, uint64_t* out, int* status);
+int plonk_g2_to_bytes(int curve, const uint64_t* in, int encoding, uint8_t* out);
 /* Use n_bases points already in HBM (PLONK_BASES_XY) as the SRS without a host round trip; they are
  * re-encoded into the library's resident form (x || y as canonical R'-Montgomery residues in 32-bit words: 64 B / 96 B per point), the caller keeps its buffer. */
 int plonk_init_dev(plonk_ctx* ctx, const void* d_bases_xy, size_t n_bases, size_t domain_size,
