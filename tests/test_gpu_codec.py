@@ -4,7 +4,8 @@ tests/codec_ref.py, bit for bit: round trips of SRS points in both forms at one 
 seeded random x with every flag; the named values (0, 1, q - 1, q, the largest 30-bit-short value, infinity and its malformed forms, both
 flags, an off-curve pair, a sign bit where none belongs); scalars around r; odd strides, poisoned gaps, a shared status word; three enqueued
 decodes; count 0 and every argument error; whole proofs with one bad element in the middle; an SRS loaded from bytes.
-tests/test_hostemu_codec.py runs a selection of this file on the CPU."""
+tests/test_hostemu_codec.py runs a selection of this file on the CPU; tools/fuzz_abi.py (`--only codec`, `--only proof_bytes`) draws the
+same entry points with random offsets, strides, element kinds and several defects per batch."""
 import random
 
 import numpy as np

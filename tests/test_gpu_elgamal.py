@@ -7,7 +7,8 @@ points and one off the curve; whole encryptions and decryptions with an E of sma
 three launches under alternating Rescue tables that are only enqueued; plonk_trim, count 0 and every argument error.
 
 The reference costs ~3 ms per permutation and ~7 ms per scalar multiplication, so each kind of expected value is computed once per curve
-for a few distinct operands, and the lanes of a launch repeat them.  tests/test_hostemu_elgamal.py runs a selection of this file on the CPU."""
+for a few distinct operands, and the lanes of a launch repeat them.  tests/test_hostemu_elgamal.py runs a selection of this file on the CPU;
+tools/fuzz_abi.py (`--ops wire`) draws the same kernels with random lengths, counts, tables and spoiled ciphertexts between other work."""
 import random
 
 import numpy as np

@@ -380,6 +380,18 @@ def test_differential_fuzz_slice_of_the_curve_operations(emu_env):
     assert r.returncode == 0 and "fuzz ok: 12 operations" in r.stdout, (r.stdout + r.stderr)[-2000:]
 
 
+def test_differential_fuzz_slice_of_the_wire_operations(emu_env):
+    """The fuzzer's `wire` group — the Rescue sponge and stream enqueued under two tables in turn, ElGamal on device pointers with spoiled E
+    and the shared-key buffer replaced between enqueued launches, the sponge / stream / encryption gadgets solved and spoiled, the byte codec
+    under drawn offsets, strides and element kinds or a commit key loaded from bytes, batches of serialized proofs with drawn defects — with
+    plonk_trim, transforms, MSMs and rounds under new commit keys between them, on one long-lived (emulated) context, against
+    tests/elgamal_ref.py, edwards_ref.py, rescue_ref.py, codec_ref.py, hint_ref.py and oracle/verifier_ref.py.  The seeds of
+    tests/test_gpu_fuzz_slice.py pin the draw counts and branches; this one runs where no GPU exists."""
+    r = subprocess.run([sys.executable, "tools/fuzz_abi.py", "--seconds", "800", "--max-ops", "12", "--seed", "11", "--max-log", "8", "--ops", "wire,trim,ntt,msm,round1"],
+                       cwd=ROOT, env=emu_env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0 and "fuzz ok: 12 operations" in r.stdout, (r.stdout + r.stderr)[-2000:]
+
+
 def test_second_device_of_one_process_raises_its_own_lds_limits(emu_env):
     """The emulation enforces the runtime's dynamic-LDS rule per (device, kernel): a launch above 64 KiB aborts unless
     hipFuncSetAttribute(MaxDynamicSharedMemorySize) was called for that kernel ON THAT DEVICE.  A second worker on another device of the

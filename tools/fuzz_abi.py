@@ -6,7 +6,7 @@ forced options in between, every result compared bit-for-bit with its reference.
 
     python tools/fuzz_abi.py --seconds 600 [--seed 1] [--curve bn254|bls12_381|both] [--max-log 13] [--ops NAME[,NAME...]] [--only NAME] [--trace]
 
-Twenty-nine operations in three groups.  `core` (nineteen, against oracle/oracle.py): transforms, MSMs and batched commitments, polynomial
+Thirty-four operations in four groups.  `core` (nineteen, against oracle/oracle.py): transforms, MSMs and batched commitments, polynomial
 operations, the grand product, quotient evaluations, distributed transforms, refused SRSs, trim, whole proofs handed to the verifier.
 `circuit` (six): circuit_preprocess (plonk_circuit_permutation_dev / _witness_dev / _check_dev against a stable argsort and a big-integer gate
 evaluation), solve (the level-by-level witness solver, plain or hinted, against tests/solve_ref.py / hint_ref.py, with planted cycles,
@@ -18,16 +18,26 @@ edwards (the mul / fixed_mul / add / check kernels alone or enqueued back to bac
 another generator or an isomorphic scaled curve, with the output over an input and the generator's table rebuilt between launches), schnorr
 (keygen, sign and verify of up to six signatures with one drawn defect), edwards_gadgets (a random chain of the builder's point gadgets solved,
 preprocessed and spoiled) and replay (the recorded solve schedule and K replayed witnesses of a layered circuit under two fuse widths, with
-planted cycles).  --ops takes operation and group names and draws from that list (default: all; `--ops core` is draw for draw the fuzzer as
-it was before the circuit group); --only runs one operation.  Whatever --max-log says, a circuit operation stays below 2^12 gates and about
-200 reference Rescue permutations, and a curve operation below 2^10 points and 24 fresh reference scalar multiplications, so that no draw
-waits long for its reference.  The final line counts the operations drawn (`per op`) and the branches the curve operations took (`branches`).
+planted cycles).  `wire` (five, against tests/elgamal_ref.py, edwards_ref.py, rescue_ref.py, codec_ref.py, hint_ref.py and
+oracle/verifier_ref.py): sponge_stream (the Rescue sponge and the counter-mode stream, two or three launches enqueued under two Rescue tables
+in turn, in place and with a guard element), elgamal (keygen, encrypt_dev and decrypt_dev enqueued back to back under a drawn parameter set
+and Rescue table, with spoiled E, a moved ciphertext element, a refused r and the context's key buffer replaced between enqueued launches),
+wire_gadgets (a chain of the builder's rescue_sponge / rescue_stream gadgets, or elgamal_circuit on ciphertexts made on the device, solved and
+spoiled), codec (G1 and Fr elements of every good and malformed kind through the decoders and encoders under drawn offsets and strides in
+poisoned buffers, or a commit key loaded from bytes and refused by index) and proof_bytes (batches of serialized proofs with one drawn defect
+each through plonk_proofs_from_bytes_dev and verifier.batch_verify_bytes).  --ops takes operation and group names and draws from that list
+(default: all; `--ops core` is draw for draw the fuzzer as it was before the circuit group); --only runs one operation.  Whatever --max-log
+says, a circuit operation stays below 2^12 gates and about 200 reference Rescue permutations, a curve or wire operation below 2^10 points or
+elements, 24 fresh reference scalar multiplications, 36 sponge or keystream permutations and 24 distinct encodings — the encryption circuit
+of wire_gadgets alone is as large as it is, 2^13 gates per ciphertext —, so that no draw waits long for its reference.  The final line counts
+the operations drawn (`per op`) and the branches the curve and wire operations took (`branches`); with two curves a line per curve before it
+(`branches on <curve>`) holds that curve's own counters.
 
 It drives whatever library `distributed_plonk_amd._ffi` loads: libplonk_hip.so on an MI355X, or — in the GPU-less build container —
 the host emulation (tests/hostemu; PLONK_HIP_LIB=tests/hostemu/_build/plain/libplonk_hostemu.so PLONK_ALLOW_HOSTEMU=1), where it
 is also worth running against the AddressSanitizer build.  The first mismatch prints the operation and its parameters (enough to
 replay it with --seed and the same --ops / --only) and exits 1; a HIP error or any unexpected exception ends the run.
-tests/test_hostemu.py runs three short fixed-seed slices of it in the CPU suite, tests/test_gpu_fuzz_slice.py nine on the device.
+tests/test_hostemu.py runs four short fixed-seed slices of it in the CPU suite, tests/test_gpu_fuzz_slice.py thirteen on the device.
 """
 import argparse
 import os
@@ -60,7 +70,8 @@ class Fuzz:
         self.branches = {}                            # which branches the curve operations took (hit)
         self._ed = None                               # ed_pool's operands and reference caches
         self.ed_fresh = 0                             # reference scalar multiplications computed by the current operation
-        for name in ("init", "init_dev"):
+        self._wire = None                             # codec_pool's points, blobs and cached reference decodings
+        for name in ("init", "init_dev", "init_bytes"):
             setattr(self.w, name, self._counting(getattr(self.w, name)))
 
     def _counting(self, install):
@@ -1810,12 +1821,890 @@ class Fuzz:
         self.hit("replay.hints" if built.has_hints else "replay.no hints")
         return bool(ok), info
 
+    # ---------------------------------------------------------------- the sponge and ElGamal, the byte codec, verification from bytes
+    # The same economy as above: a Rescue permutation costs the reference about 3 ms, a scalar multiplication 7 ms, a BLS12-381 subgroup test
+    # in Python 10 ms.  An operation computes a bounded number of fresh values — WIRE_PERMS keystream / sponge permutations, ED_BUDGET scalar
+    # multiplications, WIRE_BLOBS distinct encodings (their decodings are cached by their bytes) — and the lanes of a launch repeat them.
+    WIRE_PERMS = 36
+    WIRE_BLOBS = 24
+    POISON = 0xA5
+
+    def wire_count(self, cap):
+        rs = self.rs
+        return int(rs.choice([x for x in self.ED_COUNTS if x <= cap])) if rs.rand() < 0.6 else int(rs.randint(1, min(600, cap) + 1))
+
+    def other_rescue(self):
+        """the default tables with every round key moved, another table of the same structure (tests/test_gpu_elgamal.py: other_rescue)
+        -> (RescueParams, the reference's params)"""
+        from distributed_plonk_amd import rescue as RS
+        from tests import rescue_ref as R
+        M, K = R.default_params(self.curve)
+        K2 = [[(x + 1000 * t + i + 1) % R.MODULI[self.curve] for i, x in enumerate(row)] for t, row in enumerate(K)]
+        return RS.RescueParams(self.curve, M, K2), (M, K2)
+
+    def op_sponge_stream(self):
+        """plonk_rescue_sponge_dev and plonk_rescue_stream_dev: two or three launches enqueued without a synchronisation between them, under
+        the default Rescue table and another one in turn; L in 1 .. 10, counts around the workgroup size; the sponge on all-zero, all r - 1
+        and random messages with n_out in 1 .. 3; the stream there or back, in place or not, with a poisoned guard element behind the output
+        and, now and then, texts whose blocks lie in two workgroups.  Every lane against tests/elgamal_ref.py."""
+        from distributed_plonk_amd import rescue as RS
+        from tests import elgamal_ref as G
+        rs, curve, r = self.rs, self.curve, self.f.p
+        cap = 1 << min(self.max_log, 10)
+        tables = [(RS.RescueParams.default(curve), None, "default"), self.other_rescue() + ("other",)]
+        first = int(rs.randint(0, 2))
+        n_launch = int(rs.randint(2, 4))
+        guard = np.full((1, 4), 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+        info = dict(launches=[])
+        els = []
+        for i in range(n_launch):
+            rp, ref, table = tables[(first + i) % 2]
+            kind = "sponge" if rs.rand() < 0.5 else "stream"
+            L = int(rs.randint(1, 11))
+            count = self.wire_count(cap)
+            if kind == "stream" and rs.rand() < 0.25:                 # three blocks per text and 256 lanes per workgroup: text 85 lies in two
+                L, count = int(rs.randint(7, 10)), min(cap, max(count, 86))
+            nblocks = (L + 2) // 3
+            distinct = max(3, min(6, self.WIRE_PERMS // n_launch // nblocks))
+            el = dict(kind=kind, L=L, count=count, rp=rp, table=table, nblocks=nblocks)
+            if kind == "sponge":
+                el["n_out"] = n_out = int(rs.randint(1, 4))
+                rows = [[0] * L, [r - 1] * L] + [[self.big(r) for _ in range(L)] for _ in range(distinct - 2)]
+                want = [G.sponge(curve, row, n_out, ref) for row in rows]
+                idx = self.ed_lanes(count, len(rows))
+                el["arrays"] = [self.limbs([x for row in rows for x in row]).reshape(len(rows), L, 4)[idx]]
+                el["want"] = [x for j in idx for x in want[j]]
+            else:
+                el["decrypt"], el["in_place"] = bool(rs.randint(0, 2)), bool(rs.randint(0, 2))
+                keys = [0, r - 1] + [self.big(r) for _ in range(distinct - 2)]
+                ks = [G.keystream(curve, k, L, ref) for k in keys]
+                idx = self.ed_lanes(count, len(keys))
+                texts = self.fr(count * L)
+                tv = self.ints(texts)
+                sign = -1 if el["decrypt"] else 1
+                el["arrays"] = [self.limbs(keys)[idx], np.concatenate([texts, guard])]
+                el["texts"] = tv
+                el["want"] = [(tv[n * L + t] + sign * ks[j][t]) % r for n, j in enumerate(idx) for t in range(L)]
+                el["straddles"] = nblocks > 1 and 256 % nblocks != 0 and count * nblocks > 256
+            info["launches"].append({k: v for k, v in el.items() if k in ("kind", "L", "count", "table", "n_out", "decrypt", "in_place")})
+            els.append(el)
+        bufs = []
+        try:
+            for el in els:                                            # every upload first: an upload waits for the stream
+                el["in"] = [self.up(a) for a in el["arrays"]]
+                bufs += el["in"]
+                if el["kind"] == "stream" and el["in_place"]:
+                    el["out"] = el["in"][1]
+                else:
+                    n = el["count"] * (el["n_out"] if el["kind"] == "sponge" else el["L"])
+                    el["out"] = self.up(np.repeat(guard, n + 1, axis=0))
+                    bufs.append(el["out"])
+            self.w.sync()
+            for el in els:                                            # enqueued back to back, the tables switched in between
+                if el["kind"] == "sponge":
+                    RS.sponge_dev(self.w, el["rp"], el["in"][0].ptr, el["L"], el["count"], el["n_out"], el["out"].ptr)
+                else:
+                    RS.stream_dev(self.w, el["rp"], el["in"][0].ptr, el["in"][1].ptr, el["L"], el["count"], el["out"].ptr, decrypt=el["decrypt"])
+            ok = True
+            for i, el in enumerate(els):
+                n = el["count"] * (el["n_out"] if el["kind"] == "sponge" else el["L"])
+                got = el["out"].download((n + 1, 4))
+                good = self.ints(got[:n]) == el["want"] and np.array_equal(got[n:], guard)
+                if good and el["kind"] == "stream" and not el["in_place"]:      # the input is read, not written
+                    good = self.ints(el["in"][1].download((n, 4))) == el["texts"]
+                if not good:
+                    info.update(what=f"launch {i} ({el['kind']})", guard_intact=bool(np.array_equal(got[n:], guard)))
+                    ok = False
+                    break
+        finally:
+            for b in bufs:
+                b.free()
+        for el in els:
+            if el["kind"] == "sponge":
+                self.hit("sponge.L%3==0" if el["L"] % 3 == 0 else "sponge.L%3!=0")
+                self.hit(f"sponge.n_out.{el['n_out']}")
+            else:
+                self.hit("stream.decrypt" if el["decrypt"] else "stream.encrypt")
+                if el["in_place"]:
+                    self.hit("stream.in place")
+                if el["straddles"]:
+                    self.hit("stream.straddles a workgroup")
+        self.hit("rescue table switched between enqueued launches", n_launch - 1)
+        return ok, info
+
+    ELGAMAL_DEFECTS = ["none", "small order", "outside subgroup", "off curve"]
+
+    def op_elgamal(self):
+        """Key generation, elgamal.encrypt_dev and elgamal.decrypt_dev on device pointers, enqueued back to back and synchronised once at the
+        end, under a drawn Edwards parameter set and a drawn Rescue table: decryption keys from the edge scalars and random ones, the
+        ciphertexts of two or three fresh encryptions repeated over the lanes, up to three lanes whose E is replaced before the decryption
+        (a point of small order, a point outside the subgroup, a point off the curve: flags 0, message not compared), one ciphertext element
+        moved by a delta that the decrypted element must follow.  E, ct, the stream keys, the messages and the flags against
+        tests/elgamal_ref.py.  By coin elgamal.encrypt is first handed an r >= l (ValueError, nothing disturbed), and a dh_key_dev of one or two
+        pairs is enqueued on the trimmed context in front of the chain, whose larger count replaces the context's key buffer behind it."""
+        from distributed_plonk_amd import edwards as ED
+        from distributed_plonk_amd import elgamal as EG
+        from tests import edwards_ref as E
+        from tests import elgamal_ref as G
+        rs, curve, pool = self.rs, self.curve, self.ed_pool()
+        r, l = E.MODULI[curve], E.PARAMS[curve]["l"]
+        cap = 1 << min(self.max_log, 10)
+        pset = self.ed_param_set()
+        prm, ref, to_set = pset["prm"], pset["ref"], pset["to_set"]
+        rp, ref_rescue, table = self.rescue_params()
+        L = int(rs.randint(1, 8))
+        count = self.wire_count(cap)
+        distinct = min(count, int(rs.randint(2, 4)))
+        Gp = (ref or E.PARAMS[curve])["G"]
+        dks = [pool["scalars"][int(rs.randint(0, len(pool["scalars"])))] if rs.rand() < 0.5 else self.big(r) for _ in range(distinct)]
+        rands = [[0, 1, l - 1][int(rs.randint(0, 3))] if rs.rand() < 0.2 else self.big(l) for _ in range(distinct)]
+        msgs = [[[0, r - 1][int(rs.randint(0, 2))] if rs.rand() < 0.15 else self.big(r) for _ in range(L)] for _ in range(distinct)]
+        refuse, in_place_enc, in_place_dec = rs.rand() < 0.3, bool(rs.randint(0, 2)), bool(rs.randint(0, 2))
+        grow = count >= 2 and rs.rand() < 0.35
+        small = int(rs.randint(1, min(count, 3))) if grow else 0
+        info = dict(params=pset["name"], table=table, L=L, count=count, distinct=distinct, refuse=refuse, in_place=(in_place_enc, in_place_dec), small=small)
+        # the reference, once per distinct ciphertext
+        self.ed_fresh = 0
+        eks = [G.keygen(curve, dk, ref) for dk in dks]
+        keys = [G.dh_key(curve, x, ek, ref, ref_rescue) for x, ek in zip(rands, eks)]
+        Es = [E.mul(curve, x, Gp, ref) for x in rands]
+        cts = [G.stream(curve, k, m, False, ref_rescue) for k, m in zip(keys, msgs)]
+        self.ed_fresh += 3 * distinct
+        for j in range(distinct):
+            if G.decrypt(curve, dks[j], (Es[j], cts[j]), ref, ref_rescue) != (msgs[j], True):
+                info.update(what="the reference does not decrypt its own ciphertext", j=j)
+                return False, info
+            self.ed_fresh += 2
+        idx = self.ed_lanes(count, distinct)
+        want_msg = [list(msgs[j]) for j in idx]
+        want_flags = [3] * count
+        # up to three lanes with another E
+        cands = list(dict.fromkeys([0, count - 1, 63 % count, 64 % count, 255 % count, 256 % count, int(rs.randint(0, count))]))
+        lanes = [cands[int(i)] for i in rs.permutation(len(cands))[:int(rs.randint(0, 4))]]
+        defects, patch_E = [], []
+        for lane in lanes:
+            kind = self.ELGAMAL_DEFECTS[int(rs.randint(1, 4))]
+            j = idx[lane]
+            if kind == "small order":
+                Ep = to_set(pool["small"][int(rs.choice([2, 4, 8]))])
+            elif kind == "outside subgroup":
+                Ep = E.add(curve, Es[j], to_set(pool["small"][int(rs.choice([2, 4, 8]))]), ref)
+            else:
+                Ep = (Es[j][0], (Es[j][1] + 1) % r)
+                while E.on_curve(curve, Ep, ref):
+                    Ep = (Ep[0], (Ep[1] + 1) % r)
+            back, sub = G.decrypt(curve, dks[j], (Ep, cts[j]), ref, ref_rescue)
+            self.ed_fresh += 2
+            if kind == "off curve":
+                want_msg[lane], want_flags[lane] = None, 0
+            else:
+                if sub or not E.on_curve(curve, Ep, ref):
+                    info.update(what=f"the reference takes the {kind} point for a subgroup point", lane=lane)
+                    return False, info
+                want_msg[lane], want_flags[lane] = back, 1
+            defects.append(kind)
+            patch_E.append(Ep)
+        info.update(lanes=lanes, defects=defects, fresh_references=self.ed_fresh)
+        shift = None
+        open_lanes = [n for n in range(count) if want_msg[n] is not None]
+        if open_lanes and rs.rand() < 0.5:
+            lane, t, delta = open_lanes[int(rs.randint(0, len(open_lanes)))], int(rs.randint(0, L)), 1 + self.big(r - 1)
+            shift = (lane, t, delta)
+            want_msg[lane] = list(want_msg[lane])
+            want_msg[lane][t] = (want_msg[lane][t] + delta) % r
+            info["shift"] = (lane, t)
+        dk_l, r_l = self.limbs([dks[j] for j in idx]), self.limbs([rands[j] for j in idx])
+        msg_l = self.limbs([x for j in range(distinct) for x in msgs[j]]).reshape(distinct, L, 4)[idx]
+        ok = True
+        if refuse:                                                    # refused on the host, before anything reaches the device
+            bad_r = r_l.copy()
+            bad_lane = int(rs.randint(0, count))
+            bad_r[bad_lane] = self.limbs([[l, l + 1, r - 1][int(rs.randint(0, 3))]])[0]
+            try:
+                EG.encrypt(self.w, prm, self.pts_limbs([eks[j] for j in idx]), msg_l, bad_r, rp)
+                ok = False
+            except ValueError as ex:
+                ok = f"r[{bad_lane}] >= l" in str(ex)
+            if not ok:
+                info.update(what="an r >= l is not refused")
+                return False, info
+        if grow:
+            self.w.trim()                                             # the context's key buffer is gone: the small launch makes one of its own size
+        bufs = []
+        alloc = lambda n: bufs.append(self.w.alloc(max(n, 32))) or bufs[-1]
+        try:
+            d_dk, d_r, d_msg = (self.up(a) for a in (dk_l, r_l, msg_l))
+            bufs += [d_dk, d_r, d_msg]
+            d_pE = d_pc = d_ss = d_sp = d_sk = None
+            if patch_E:
+                d_pE = self.up(self.pts_limbs(patch_E))
+                bufs.append(d_pE)
+            if shift:
+                lane, t, delta = shift
+                d_pc = self.up(self.limbs([(cts[idx[lane]][t] + delta) % r]))
+                bufs.append(d_pc)
+            if grow:
+                d_ss, d_sp, d_sk = self.up(r_l[:small]), self.up(self.pts_limbs([eks[j] for j in idx[:small]])), alloc(small * 32)
+                bufs += [d_ss, d_sp]
+            d_ek, d_E, d_keys, d_keys2, d_E0, d_ct0, d_flags = (alloc(count * n) for n in (64, 64, 32, 32, 64, L * 32, 4))
+            d_ct = d_msg if in_place_enc else alloc(count * L * 32)
+            d_back = d_ct if in_place_dec else alloc(count * L * 32)
+            self.w.sync()
+            if grow:
+                EG.dh_key_dev(self.w, prm, rp, d_ss.ptr, d_sp.ptr, small, d_sk.ptr)
+            ED.fixed_mul_dev(self.w, prm, d_dk.ptr, count, d_ek.ptr)
+            EG.encrypt_dev(self.w, prm, d_ek.ptr, d_msg.ptr, d_r.ptr, L, count, d_E.ptr, d_ct.ptr, d_keys.ptr, rp)
+            self.w.memcpy_d2d_async(d_E0.ptr, d_E.ptr, count * 64)
+            self.w.memcpy_d2d_async(d_ct0.ptr, d_ct.ptr, count * L * 32)
+            for n, lane in enumerate(lanes):
+                self.w.memcpy_d2d_async(d_E.ptr + lane * 64, d_pE.ptr + n * 64, 64)
+            if shift:
+                self.w.memcpy_d2d_async(d_ct.ptr + (shift[0] * L + shift[1]) * 32, d_pc.ptr, 32)
+            EG.decrypt_dev(self.w, prm, d_dk.ptr, d_E.ptr, d_ct.ptr, L, count, d_back.ptr, d_flags.ptr, d_keys2.ptr, rp)
+            self.w.sync()
+            checks = [("keygen", lambda: self.pts_ints(d_ek.download((count, 2, 4))) == [eks[j] for j in idx]),
+                      ("E", lambda: self.pts_ints(d_E0.download((count, 2, 4))) == [Es[j] for j in idx]),
+                      ("ct", lambda: self.ints(d_ct0.download((count * L, 4))) == [x for j in idx for x in cts[j]]),
+                      ("stream keys", lambda: self.ints(d_keys.download((count, 4))) == [keys[j] for j in idx]),
+                      ("flags", lambda: d_flags.download((count,), dtype=np.uint32).tolist() == want_flags)]
+            if grow:
+                checks.append(("the small launch's keys", lambda: self.ints(d_sk.download((small, 4))) == [keys[j] for j in idx[:small]]))
+            for what, check in checks:
+                if not check():
+                    info.update(what=what)
+                    ok = False
+                    break
+            if ok:
+                back = self.ints(d_back.download((count * L, 4)))
+                bad = [n for n in range(count) if want_msg[n] is not None and back[n * L:(n + 1) * L] != want_msg[n]]
+                if bad:
+                    info.update(what="messages", first_bad_lane=bad[0], bad_lanes=len(bad))
+                    ok = False
+        finally:
+            for b in bufs:
+                b.free()
+        self.hit("elgamal.params." + pset["name"])
+        self.hit("elgamal.table." + table)
+        for kind in defects:
+            self.hit("elgamal.defect." + kind)
+        if len(set(lanes)) < count:
+            self.hit("elgamal.defect.none")
+        if shift:
+            self.hit("elgamal.ct shifted")
+        if in_place_enc or in_place_dec:
+            self.hit("elgamal.in place")
+        if refuse:
+            self.hit("elgamal.r>=l refused")
+        if grow:
+            self.hit("elgamal.key buffer grown between enqueued launches")
+        return ok, info
+
     CORE_OPS = ["ntt", "coset_eval_interp", "msm", "commit_many", "poly", "lincomb", "perm_product", "transpose", "distributed_fft", "quotient", "compact_rows_fft", "round1", "prove_verify", "class_prove", "msm_table",
                 "perm_product_ranges", "class_ifft", "init_refuses_bad_srs", "trim"]
     CIRCUIT_OPS = ["circuit_preprocess", "solve", "rescue", "accumulator", "verify_batch", "membership"]
     CURVE_OPS = ["edwards", "schnorr", "edwards_gadgets", "replay"]
-    OPS = CORE_OPS + CIRCUIT_OPS + CURVE_OPS
-    GROUPS = {"core": CORE_OPS, "circuit": CIRCUIT_OPS, "curve": CURVE_OPS}
+    WIRE_SPOILS = ["message", "r", "ct", "E"]
+
+    def op_wire_gadgets(self):
+        """Either a chain of one to three of the builder's rescue_sponge (L in 1 .. 7, n_out in 1 .. 3) and rescue_stream (1 .. 3 blocks)
+        gadgets over m <= 3 instances, each fed by the one before and the last output enforced equal to a public input — as many
+        permutations as fit below 2^min(max_log, 12) gates —, or elgamal.elgamal_circuit(curve, m, L) with m <= 2 (two in a quarter of the
+        draws) and L in 1 .. 4, about 7 300 gates and 1 080 levels per encryption whatever --max-log says, its witness inputs taken from keys
+        and ciphertexts made ON THE DEVICE, under a drawn Edwards parameter set.  Both under a drawn Rescue table.  solve_dev against
+        HintRefSolver variable for variable, with the level and evaluation counters, and the chain's outputs against tests/elgamal_ref.py;
+        then, by coin, one spoiled value (a message element; for the encryption circuit also r, a public ct element, the public E), for
+        which preprocess(check=True) must name the reference's first unsatisfied gate."""
+        from distributed_plonk_amd import builder as BD
+        from distributed_plonk_amd import circuit as CI
+        from distributed_plonk_amd import elgamal as EG
+        from tests import edwards_ref as E
+        from tests import elgamal_ref as G
+        from tests.hint_ref import GIVEN, HintRefSolver
+        rs, curve, r = self.rs, self.curve, self.f.p
+        which = "elgamal_circuit" if rs.rand() < 0.5 else "chain"
+        rp, ref_rescue, table = self.rescue_params()
+        info = dict(which=which, table=table)
+        taken = []
+        if which == "chain":
+            budget = max(1, ((1 << min(self.max_log, 12)) - 64) // 148)          # permutations x instances below the gate cap
+            m = min(int(rs.randint(1, 4)), budget)
+            left = budget // m
+            b = BD.CircuitBuilder(curve)
+            out_pub = b.public_input(m)
+            n_in = int(rs.randint(1, 8))
+            avail = [np.atleast_1d(b.input(m)) for _ in range(n_in)]
+            vals = [[[0, r - 1][int(rs.randint(0, 2))] if rs.rand() < 0.15 else self.big(r) for _ in range(m)] for _ in range(n_in)]
+            values = [x for col in vals for x in col]
+            last = 0                                                  # every gadget reads the one before it; the first reads input 0
+            chain = []
+            for _ in range(int(rs.randint(1, 4))):
+                if left < 1:
+                    break
+                pick = lambda: int(rs.randint(0, len(avail)))
+                if rs.rand() < 0.5:
+                    L = int(rs.randint(1, min(7, 3 * left) + 1))
+                    n_out = int(rs.randint(1, 4))
+                    src = [last] + [pick() for _ in range(L - 1)]
+                    outs = b.rescue_sponge([avail[i] for i in src], n_out, rp)
+                    want = [G.sponge(curve, [vals[i][k] for i in src], n_out, ref_rescue) for k in range(m)]
+                    left -= (L + 2) // 3
+                    chain.append(("sponge", L, n_out))
+                    taken.append("sponge")
+                else:
+                    nb = int(rs.randint(1, min(3, left) + 1))
+                    outs = [v for blk in b.rescue_stream(avail[last], nb, rp) for v in blk]
+                    want = [[x for j in range(nb) for x in G.stream_block(curve, vals[last][k], j, ref_rescue)] for k in range(m)]
+                    left -= nb
+                    chain.append(("stream", nb))
+                    taken.append("stream")
+                for t, o in enumerate(outs):
+                    avail.append(np.atleast_1d(o))
+                    vals.append([want[k][t] for k in range(m)])
+                last = len(avail) - 1 - int(rs.randint(0, len(outs)))
+            b.enforce_equal(avail[last], out_pub)
+            built = b.build()
+            publics = list(vals[last])
+            outputs = [(avail[i], vals[i]) for i in range(n_in, len(avail))]
+            spoil = str(rs.choice(["none", "message"]))
+            k = int(rs.randint(0, m))
+            at = ("inputs", k)                                        # input 0 of instance k: the chain hangs on it
+            info.update(m=m, inputs=n_in, chain=chain, n=built.n, spoil=spoil)
+        else:
+            m = 2 if rs.rand() < 0.25 else 1
+            L = int(rs.randint(1, 5))
+            pset = self.ed_param_set()
+            prm, ref = pset["prm"], pset["ref"]
+            l = E.PARAMS[curve]["l"]
+            spoil = str(rs.choice(["none"] + self.WIRE_SPOILS))
+            k, t = int(rs.randint(0, m)), int(rs.randint(0, L))
+            info.update(m=m, L=L, params=pset["name"], spoil=spoil)
+            built = EG.elgamal_circuit(curve, m, L, prm, rp)
+            info["n"] = built.n
+            dk = self.limbs([1 + self.big(l - 1) for _ in range(m)])
+            rand = self.limbs([self.big(l) for _ in range(m)])
+            msg = self.limbs([[0, r - 1][int(rs.randint(0, 2))] if rs.rand() < 0.15 else self.big(r) for _ in range(m * L)]).reshape(m, L, 4)
+            ek = EG.keygen(self.w, prm, dk)
+            Ep, ct = EG.encrypt(self.w, prm, ek, msg, rand, rp)
+            inputs, public = EG.elgamal_witness_inputs(ek, rand, msg, (Ep, ct))
+            values, publics = self.ints(inputs), self.ints(public)
+            outputs = []
+            at = dict(message=("inputs", m + t * m + k), r=("inputs", k), ct=("publics", 4 * m + t * m + k), E=("publics", 2 * m + k)).get(spoil)
+            taken.append("elgamal_circuit")
+        ref_solver = HintRefSolver(built, values, publics)
+        want, _ = ref_solver.solve()
+        try:
+            if ref_solver.unsatisfied_gates(want):                    # the chain's own promise, or the device's ciphertext before the circuit's definition
+                info.update(what="the reference finds the unspoiled circuit unsatisfied", first_unsatisfied=ref_solver.unsatisfied_gates(want)[0])
+                return False, info
+            if any(want[int(ids[i])] != col[i] for ids, col in outputs for i in range(m)):
+                info.update(what="the solved gadget outputs differ from tests/elgamal_ref.py")
+                return False, info
+            s = built.solve_dev(self.w, self.limbs(values), self.limbs(publics))
+            try:
+                info["what"] = "solve"
+                ok = (np.array_equal(s.witness(), ref_solver.limbs(want)) and s.levels == ref_solver.depth()
+                      and s.evaluations == int((built.def_gate != GIVEN).sum()))
+            finally:
+                s.close()
+            unsat = []
+            if ok and spoil != "none":
+                v2, p2 = list(values), list(publics)
+                if spoil == "r":
+                    v2[at[1]] = (v2[at[1]] + 1) % l
+                elif spoil == "E":                                    # another point of the curve: 2 E, or G where E is the identity
+                    P = (p2[at[1]], p2[at[1] + m])
+                    Q = E.add(curve, P, P, ref)
+                    Q = (ref or E.PARAMS[curve])["G"] if Q == P else Q
+                    p2[at[1]], p2[at[1] + m] = Q
+                else:
+                    tgt = v2 if at[0] == "inputs" else p2
+                    tgt[at[1]] = (tgt[at[1]] + 1 + self.big(r - 1)) % r
+                ref2 = HintRefSolver(built, v2, p2)
+                unsat = ref2.unsatisfied_gates(ref2.solve()[0])
+                info.update(what="preprocess", first_unsatisfied=unsat[0] if unsat else -1)
+                try:
+                    built.preprocess(self.w, self.limbs(v2), self.limbs(p2), check=True).close()
+                    ok = not unsat
+                except CI.UnsatisfiedCircuit as ex:
+                    info["reported"] = ex.gate
+                    ok = bool(unsat) and ex.gate == unsat[0] and ex.position == -1
+        finally:
+            built.close()
+        for name in set(taken):
+            self.hit("wire_gadget." + name)
+        if spoil != "none" and unsat:
+            self.hit("wire_gadget.spoil." + spoil)
+        return bool(ok), info
+
+    # -- the byte codec
+    def fq_pts(self, xy):
+        """(count, 2Q) Montgomery limbs of G1 points -> integer pairs, None for (0, 0)"""
+        from distributed_plonk_amd.transcript import FQ_MODULI
+        q, n = FQ_MODULI[self.curve], self.w.q64
+        r_inv = pow(pow(2, 64 * n, q), -1, q)
+        val = lambda l: int.from_bytes(np.ascontiguousarray(l, dtype=np.uint64).tobytes(), "little") * r_inv % q
+        return [None if not row.any() else (val(row[:n]), val(row[n:])) for row in np.ascontiguousarray(xy, dtype=np.uint64).reshape(-1, 2 * n)]
+
+    def synth_points(self, tau, n):
+        """tau^i G for i < n, made on the device (plonk_synth_srs): (n, 2Q) limbs"""
+        d = self.w.alloc(n * 16 * self.w.q64)
+        try:
+            self.w.synth_srs(self.f.to_limbs(tau % self.f.p or 7), n, d.ptr)
+            self.w.sync()
+            return d.download((n, 2 * self.w.q64))
+        finally:
+            d.free()
+
+    def codec_pool(self):
+        """Once per Fuzz object: 32 device-made SRS points as integer pairs (both signs of y occur), an x that no point has, on BLS12-381 three
+        curve points outside the r-subgroup ((0, 2) of order 3 and two from seeded x), and the cache of the reference's decodings by their
+        bytes — a subgroup test costs Python about 10 ms, and the lanes of a launch repeat their blobs."""
+        if self._wire is None:
+            import random
+            from distributed_plonk_amd.transcript import FQ_MODULI
+            from tests import codec_ref as R
+            curve = self.curve
+            q, nb = FQ_MODULI[curve], R.NBYTES[curve]
+            rnd = random.Random("fuzz codec " + curve)
+            pts = self.fq_pts(self.synth_points(rnd.randrange(2, self.f.p), 32))
+            assert {p[1] > q - p[1] for p in pts} == {True, False}
+            no_point = next(x for x in range(2, 100) if R.g1_decode(curve, x.to_bytes(nb, "little"), "compressed", False)[1] == 1)
+            outside = []
+            if curve == "bls12_381":
+                outside = [(0, 2)]
+                while len(outside) < 3:
+                    P, st = R.g1_decode(curve, rnd.randrange(q).to_bytes(nb, "little"), "compressed", False)
+                    if st == 0 and not R.g1_in_subgroup(curve, P):
+                        outside.append(P)
+            self._wire = dict(points=pts, no_point=no_point, outside=outside, decoded={})
+        return self._wire
+
+    def g1_ref(self, blob, encoding, check_subgroup):
+        """tests/codec_ref.py's g1_decode, cached by the bytes"""
+        from tests import codec_ref as R
+        cache = self.codec_pool()["decoded"]
+        key = (bytes(blob), encoding, bool(check_subgroup))
+        if key not in cache:
+            cache[key] = R.g1_decode(self.curve, key[0], encoding, check_subgroup)
+        return cache[key]
+
+    CODEC_KINDS = ["valid", "infinity", "random x", "x >= q", "both flags", "infinity with non-zero bytes", "sign bit on a pair", "off-curve pair",
+                   "outside subgroup"]
+
+    def codec_blob(self, kind, encoding):
+        """one element of the kind in the encoding"""
+        from distributed_plonk_amd.transcript import FQ_MODULI
+        from tests import codec_ref as R
+        rs, curve, pool = self.rs, self.curve, self.codec_pool()
+        q, nb = FQ_MODULI[curve], R.NBYTES[curve]
+        unc = encoding == "uncompressed"
+        le = lambda v: v.to_bytes(nb, "little")
+        flag = lambda b, f: b[:-1] + bytes([b[-1] | f])
+        P = pool["points"][int(rs.randint(0, len(pool["points"])))]
+        if kind == "valid":
+            return R.g1_encode(curve, P, encoding)
+        if kind == "infinity":
+            return R.g1_encode(curve, None, encoding)
+        if kind == "random x":                                        # and a random flag byte; in a pair the y of x, where it has one, by coin
+            x = self.big(q)
+            f = int(rs.randint(0, 4)) << 6
+            if not unc:
+                return flag(le(x), f)
+            Q, st = self.g1_ref(le(x), "compressed", False)
+            return le(x) + flag(le(Q[1] if st == 0 and rs.rand() < 0.5 else self.big(q)), f)
+        if kind == "x >= q":                                          # q itself or anything up to the 30 bits short of the last word
+            big = q if rs.rand() < 0.3 else q + self.big((1 << (8 * nb - 2)) - q)
+            if not unc:
+                return flag(le(big), int(rs.randint(0, 2)) << 7)
+            return le(big) + le(P[1]) if rs.rand() < 0.5 else le(P[0]) + le(big)
+        if kind == "both flags":
+            return flag(R.g1_encode(curve, P, encoding), 0xC0)
+        if kind == "infinity with non-zero bytes":
+            if not unc:
+                return flag(le(1 + self.big(q - 1) if rs.rand() < 0.5 else 1 << int(rs.randint(0, 8 * nb - 2))), 0x40)
+            a, b = (0, 1 + self.big(q - 1)) if rs.rand() < 0.5 else (1 << int(rs.randint(0, 8 * nb - 2)), 0)
+            return le(a) + flag(le(b), 0x40)
+        if kind == "sign bit on a pair":
+            return flag(R.g1_encode(curve, P, "uncompressed"), 0x80)
+        if kind == "off-curve pair":
+            return le(P[0]) + le((P[1] + 1 + int(rs.randint(0, 1 << 30))) % q)
+        Q = pool["outside"][int(rs.randint(0, len(pool["outside"])))]
+        if rs.rand() < 0.5:
+            Q = (Q[0], q - Q[1])
+        return R.g1_encode(curve, Q, encoding)
+
+    def op_codec(self):
+        """plonk_g1_from_bytes_dev / _to_bytes_dev, plonk_fr_from_bytes_dev / _to_bytes_dev and plonk_codec_first_bad_dev on drawn element kinds
+        (CODEC_KINDS: valid points of both signs, infinity, random x under random flags, and every malformed form) in a drawn call shape —
+        encoding, subgroup check, an input offset of 0 .. 7 bytes, strides with 0 .. 9 bytes and 0 .. 3 words of gap, a status stride of 0, 1
+        or 2 — in poisoned buffers whose prefix, gaps, tail and neighbouring status words must stay as they were; limbs and status per
+        element against tests/codec_ref.py, the shared word against the OR of all, the first bad index, the re-encoding of the decoded
+        output in another drawn shape byte for byte; the same for scalars around r and 2^256 - 1.  One draw in six loads the context's commit
+        key from bytes instead (init_bytes), see codec_srs."""
+        from distributed_plonk_amd import codec as CD
+        from tests import codec_ref as R
+        rs, curve, w = self.rs, self.curve, self.w
+        if rs.rand() < 1 / 6:
+            return self.codec_srs()
+        self.codec_pool()
+        nb, n2 = R.NBYTES[curve], 2 * w.q64
+        cap = 1 << min(self.max_log, 10)
+        P8, P32, P64 = np.uint8(self.POISON), np.uint32(0xA5A5A5A5), np.uint64(0xA5A5A5A5A5A5A5A5)
+        encoding = str(rs.choice(["compressed", "uncompressed"]))
+        check = bool(rs.randint(0, 2))
+        el = nb * (2 if encoding == "uncompressed" else 1)
+        kinds = [k for k in self.CODEC_KINDS if (encoding == "uncompressed" or k not in ("sign bit on a pair", "off-curve pair"))
+                 and (curve == "bls12_381" or k != "outside subgroup")]
+        count = self.wire_count(cap)
+        distinct = min(count, self.WIRE_BLOBS)
+        drawn = [kinds[int(rs.randint(0, len(kinds)))] if rs.rand() < 0.6 else "valid" for _ in range(distinct)]
+        blobs = [self.codec_blob(k, encoding) for k in drawn]
+        idx = self.ed_lanes(count, distinct)
+        off, in_stride, out_stride, st_stride = int(rs.randint(0, 8)), el + int(rs.randint(0, 10)), n2 + int(rs.randint(0, 4)), int(rs.randint(0, 3))
+        enc2 = str(rs.choice(["compressed", "uncompressed"]))
+        el2 = nb * (2 if enc2 == "uncompressed" else 1)
+        off2, stride2 = int(rs.randint(0, 8)), el2 + int(rs.randint(0, 10))
+        info = dict(encoding=encoding, check_subgroup=check, count=count, kinds=sorted(set(drawn)), offset=off, in_stride=in_stride, out_stride=out_stride,
+                    status_stride=st_stride, encoding2=enc2, offset2=off2, out_stride2=stride2)
+        refs = [self.g1_ref(bl, encoding, check) for bl in blobs]
+        want_xy = np.array([R.g1_limbs(curve, p) for p, _ in refs], dtype=np.uint64).reshape(distinct, n2)[idx]
+        want_st = [refs[j][1] for j in idx]
+        raw = np.full(off + count * in_stride + 16, P8, np.uint8)
+        src = np.frombuffer(b"".join(blobs), np.uint8).reshape(distinct, el)[idx]
+        raw[off:off + count * in_stride].reshape(count, in_stride)[:, :el] = src
+        n_words = (count * st_stride if st_stride else 1) + 2
+        used = np.arange(count) * st_stride if st_stride else np.zeros(1, dtype=np.int64)
+        st0 = np.full(n_words, P32, np.uint32)
+        st0[used] = 0
+        back_want = np.full(off2 + count * stride2 + 16, P8, np.uint8)
+        enc_of = [np.frombuffer(R.g1_encode(curve, p, enc2), np.uint8) for p, _ in refs]
+        back_want[off2:off2 + count * stride2].reshape(count, stride2)[:, :el2] = np.stack(enc_of)[idx]
+        if enc2 == encoding and any(s == 0 and bytes(e) != bl for (_, s), e, bl in zip(refs, enc_of, blobs)):
+            info.update(what="the reference does not encode a good element to the bytes it came from")
+            return False, info
+        bufs = []
+        try:
+            d_in, d_st = self.up(raw), self.up(st0)
+            d_out, d_back = self.up(np.full(count * out_stride + 4, P64, np.uint64)), self.up(np.full(back_want.size, P8, np.uint8))
+            bufs += [d_in, d_st, d_out, d_back]
+            w.sync()
+            CD.g1_from_bytes_dev(w, d_in.ptr + off, count, d_out.ptr, d_st.ptr, encoding, check, in_stride=in_stride, out_stride_u64=out_stride,
+                                 status_stride=st_stride)
+            CD.g1_to_bytes_dev(w, d_out.ptr, count, d_back.ptr + off2, enc2, in_stride_u64=out_stride, out_stride=stride2)
+            got = d_out.download((count * out_stride + 4,))
+            st = d_st.download((n_words,), dtype=np.uint32)
+            rows = got[:count * out_stride].reshape(count, out_stride)
+            want_words = st0.copy()
+            if st_stride:
+                want_words[used] = want_st
+            else:
+                want_words[0] = int(np.bitwise_or.reduce(np.array(want_st, dtype=np.uint32)))
+            bad = [i for i, s in enumerate(want_st) if s]
+            checks = [("limbs", lambda: np.array_equal(rows[:, :n2], want_xy)),
+                      ("output gaps and tail", lambda: (rows[:, n2:] == P64).all() and (got[count * out_stride:] == P64).all()),
+                      ("status", lambda: np.array_equal(st, want_words)),
+                      ("input", lambda: np.array_equal(d_in.download((raw.size,), dtype=np.uint8), raw)),
+                      ("re-encoding", lambda: np.array_equal(d_back.download((back_want.size,), dtype=np.uint8), back_want))]
+            if st_stride:
+                checks.append(("first bad", lambda: w.codec_first_bad_dev(d_st.ptr, count, st_stride) == (bad[0] if bad else -1)))
+                cut = int(rs.randint(0, count + 1))                   # and over a prefix
+                checks.append(("first bad of a prefix", lambda: w.codec_first_bad_dev(d_st.ptr, cut, st_stride) == (bad[0] if bad and bad[0] < cut else -1)))
+            if st_stride == 1 and count >= 2:                         # every second word of a dense array
+                even = [i // 2 for i in bad if i % 2 == 0]
+                checks.append(("first bad at stride 2", lambda: w.codec_first_bad_dev(d_st.ptr, (count + 1) // 2, 2) == (even[0] if even else -1)))
+            ok = True
+            for what, check_ in checks:
+                if not check_():
+                    info.update(what=what)
+                    ok = False
+                    break
+            if ok:
+                ok, what = self.codec_fr(cap)
+                if not ok:
+                    info.update(what=what)
+        finally:
+            for b in bufs:
+                b.free()
+        self.hit("codec.g1." + encoding)
+        self.hit("codec.subgroup." + ("checked" if check else "unchecked"))
+        self.hit(f"codec.status stride.{st_stride}")
+        if off % 2:
+            self.hit("codec.odd input address")
+        for k in set(drawn):
+            self.hit("codec.kind." + k)
+        self.hit("codec.fr")
+        return ok, info
+
+    def codec_fr(self, cap):
+        """the scalar half of op_codec -> (ok, what failed)"""
+        from distributed_plonk_amd import codec as CD
+        from tests import codec_ref as R
+        rs, curve, w, r = self.rs, self.curve, self.w, self.f.p
+        P8, P32, P64 = np.uint8(self.POISON), np.uint32(0xA5A5A5A5), np.uint64(0xA5A5A5A5A5A5A5A5)
+        count = self.wire_count(cap)
+        vals = [0, 1, r - 1, r, r + 1, 2 ** 256 - 1] + [self.big(r) for _ in range(6)] + [r + self.big(2 ** 256 - r) for _ in range(2)]
+        vals = [vals[int(i)] for i in rs.permutation(len(vals))]
+        idx = self.ed_lanes(count, len(vals))
+        off, in_stride, out_stride, st_stride = int(rs.randint(0, 8)), 32 + int(rs.randint(0, 10)), 4 + int(rs.randint(0, 4)), int(rs.randint(0, 3))
+        off2, stride2 = int(rs.randint(0, 8)), 32 + int(rs.randint(0, 10))
+        refs = [R.fr_decode(curve, v.to_bytes(32, "little")) for v in vals]
+        want = np.array([R.limbs_of(curve, v or 0, "r") for v, _ in refs], dtype=np.uint64)[idx]
+        want_st = [refs[j][1] for j in idx]
+        raw = np.full(off + count * in_stride + 16, P8, np.uint8)
+        raw[off:off + count * in_stride].reshape(count, in_stride)[:, :32] = np.frombuffer(b"".join(v.to_bytes(32, "little") for v in vals), np.uint8).reshape(-1, 32)[idx]
+        n_words = (count * st_stride if st_stride else 1) + 2
+        used = np.arange(count) * st_stride if st_stride else np.zeros(1, dtype=np.int64)
+        st0 = np.full(n_words, P32, np.uint32)
+        st0[used] = 0
+        want_words = st0.copy()
+        if st_stride:
+            want_words[used] = want_st
+        else:
+            want_words[0] = int(np.bitwise_or.reduce(np.array(want_st, dtype=np.uint32)))
+        back_want = np.full(off2 + count * stride2 + 16, P8, np.uint8)
+        enc = np.frombuffer(b"".join(R.fr_encode(curve, v or 0) for v, _ in refs), np.uint8).reshape(-1, 32)[idx]
+        back_want[off2:off2 + count * stride2].reshape(count, stride2)[:, :32] = enc
+        bufs = []
+        try:
+            d_in, d_st = self.up(raw), self.up(st0)
+            d_out, d_back = self.up(np.full(count * out_stride + 4, P64, np.uint64)), self.up(np.full(back_want.size, P8, np.uint8))
+            bufs += [d_in, d_st, d_out, d_back]
+            w.sync()
+            CD.fr_from_bytes_dev(w, d_in.ptr + off, count, d_out.ptr, d_st.ptr, in_stride=in_stride, out_stride_u64=out_stride, status_stride=st_stride)
+            CD.fr_to_bytes_dev(w, d_out.ptr, count, d_back.ptr + off2, in_stride_u64=out_stride, out_stride=stride2)
+            got = d_out.download((count * out_stride + 4,))
+            rows = got[:count * out_stride].reshape(count, out_stride)
+            if not np.array_equal(rows[:, :4], want):
+                return False, "scalar limbs"
+            if not ((rows[:, 4:] == P64).all() and (got[count * out_stride:] == P64).all()):
+                return False, "scalar output gaps and tail"
+            if not np.array_equal(d_st.download((n_words,), dtype=np.uint32), want_words):
+                return False, "scalar status"
+            if not np.array_equal(d_back.download((back_want.size,), dtype=np.uint8), back_want):
+                return False, "scalar re-encoding"
+        finally:
+            for b in bufs:
+                b.free()
+        return True, None
+
+    def codec_srs(self):
+        """PlonkWorker.init_bytes on n <= 2^min(max_log, 10) device-made points encoded by the reference, in either encoding: the commit key
+        loaded from them answers an MSM like the oracle over the same points; or, by coin, one drawn point spoiled (an x that no point has,
+        an x >= q, on BLS12-381 a point outside the subgroup): a PlonkError naming the index and the status, no bases left behind (msm_dev
+        refuses), and the next SRS of the other operations installs and commits."""
+        from distributed_plonk_amd._ffi import MsmWorkload, PlonkError
+        from distributed_plonk_amd.transcript import FQ_MODULI
+        from tests import codec_ref as R
+        rs, curve, w = self.rs, self.curve, self.w
+        pool = self.codec_pool()
+        q, nb = FQ_MODULI[curve], R.NBYTES[curve]
+        n = int(rs.randint(1, (1 << min(self.max_log, 10)) + 1))
+        encoding = str(rs.choice(["compressed", "uncompressed"]))
+        check = bool(rs.randint(0, 2))
+        refuse = bool(rs.randint(0, 2))
+        xy = self.synth_points(self.big(self.f.p), n)
+        blobs = [R.g1_encode(curve, p, encoding) for p in self.fq_pts(xy)]
+        info = dict(srs=n, encoding=encoding, check_subgroup=check, refuse=refuse)
+        self.n_bases = 0                                              # whatever happens below, the shared SRS of the other operations is gone
+        if refuse:
+            i = int(rs.randint(0, n))
+            spoils = ["no point", "x >= q"] + (["outside subgroup"] if curve == "bls12_381" and check else [])
+            spoil = spoils[int(rs.randint(0, len(spoils)))]
+            if spoil == "no point":
+                P = (pool["no_point"], 1)
+            elif spoil == "x >= q":
+                P = (q, 1)
+            else:
+                P = pool["outside"][int(rs.randint(0, len(pool["outside"])))]
+            blobs[i] = P[0].to_bytes(nb, "little") + (P[1].to_bytes(nb, "little") if encoding == "uncompressed" else b"")
+            status = R.g1_decode(curve, blobs[i], encoding, check)[1]
+            info.update(i=i, spoil=spoil, status=status)
+            ok = False
+            try:
+                w.init_bytes(b"".join(blobs), n, 0, 0, encoding=encoding, check_subgroup=check)
+            except PlonkError as ex:
+                info["error"] = str(ex)[:160]
+                ok = status != 0 and ex.code == -1 and f"base {i} does not decode" in str(ex) and f"status {status}:" in str(ex)
+            if ok:
+                d = w.alloc(32)
+                try:
+                    w.msm_dev(0, 1, d.ptr)
+                    ok = False
+                    info["what"] = "bases are left behind a refused SRS"
+                except PlonkError as ex:
+                    ok = "resident bases" in str(ex)
+                finally:
+                    d.free()
+            if ok:                                                    # a following SRS installs and commits
+                m = int(rs.randint(1, 65))
+                self.ensure_bases(m)
+                sc = self.scalars(m)
+                ok = self.affine_eq(w.var_msm(MsmWorkload(0, m), sc), self.O.msm(self.cid, self.bases[:m], sc, inf=self.inf[:m], threads=4))
+                info.setdefault("what", "the SRS after the refused one")
+            self.hit("codec.srs from bytes.refused")
+            return ok, info
+        w.init_bytes(b"".join(blobs), n, 0, 0, encoding=encoding, check_subgroup=check)
+        sc = self.scalars(n)
+        ok = self.affine_eq(w.var_msm(MsmWorkload(0, n), sc), self.O.msm(self.cid, xy, sc, threads=4))
+        self.hit("codec.srs from bytes.accepted")
+        return ok, info
+
+    # -- proofs as bytes
+    PROOF_DEFECTS = ["none", "flipped sign", "no point", "outside subgroup", "scalar >= r", "non-canonical infinity", "length prefix", "two bad elements"]
+
+    def proof_ref_decode(self, blob):
+        """One serialized proof by tests/codec_ref.py -> (the proof as a dict with every bad element zeroed, status): 16 for a Vec length
+        other than 5, 5, 5, 4, OR-ed with the statuses of the 13 points (subgroup-checked) and 10 scalars"""
+        from tests import codec_ref as R
+        curve = self.curve
+        nb = R.NBYTES[curve]
+        evals = 16 + 13 * nb
+        status = 0
+        for at, want in ((0, 5), (8 + 6 * nb, 5), (evals, 5), (evals + 8 + 160, 4)):
+            if int.from_bytes(blob[at:at + 8], "little") != want:
+                status |= 16
+        pts, evs = [], []
+        for i in range(13):
+            at = (8 if i < 6 else 16) + i * nb
+            P, st = self.g1_ref(blob[at:at + nb], "compressed", True)
+            status |= st
+            pts.append((np.array(R.g1_limbs(curve, P), dtype=np.uint64), P is None))
+        for j in range(10):
+            at = evals + (8 if j < 5 else 16) + 32 * j
+            v, st = R.fr_decode(curve, blob[at:at + 32])
+            status |= st
+            evs.append(np.array(R.limbs_of(curve, v or 0, "r"), dtype=np.uint64))
+        return {"wires_poly_comms": pts[:5], "prod_perm_poly_comm": pts[5], "split_quot_poly_comms": pts[6:11], "opening_proof": pts[11],
+                "shifted_opening_proof": pts[12], "wires_evals": evs[:5], "wire_sigma_evals": evs[5:9], "perm_next_eval": evs[9]}, status
+
+    def op_proof_bytes(self):
+        """K in 1 .. 5 serialized proofs of the proved instance, each with one drawn defect (PROOF_DEFECTS: a flipped sign bit, which decodes
+        and is the verifier's to reject; an x without a point; on BLS12-381 a point outside the subgroup; a scalar >= r; an infinity with
+        other bytes set; a wrong Vec length; two bad elements of different kinds, whose bits share one status word): plonk_proofs_from_bytes_dev's
+        records and status words against the reference's decoding (tests/codec_ref.py) with exactly the bad elements zeroed, then
+        verifier.batch_verify_bytes' verdicts against oracle/verifier_ref.py on the proofs that decode, False for the rest, and
+        stats["decode_status"]."""
+        from distributed_plonk_amd import codec as CD
+        from distributed_plonk_amd import transcript as TR
+        from distributed_plonk_amd import verifier as VF
+        from distributed_plonk_amd.transcript import PlonkTranscript
+        from oracle import bigint_ref as B, verifier_ref as V
+        from tests import codec_ref as R
+        rs, curve, r = self.rs, self.curve, self.f.p
+        pr = self.proved_instance()
+        pool = self.codec_pool()
+        vk, pub0, tau = pr["vk"], np.asarray(pr["pub"], dtype=np.uint64).reshape(-1, 4), pr["tau"]
+        nb = R.NBYTES[curve]
+        evals = 16 + 13 * nb
+        point_at = lambda i: (8 if i < 6 else 16) + i * nb
+        eval_at = lambda j: evals + (8 if j < 5 else 16) + 32 * j
+        K = int(rs.randint(1, 6))
+        info = dict(log_n=pr["log_n"], num_inputs=pr["num_inputs"], seed=pr["seed"], K=K)
+        honest = [TR.serialize_proof(curve, p) for p in pr["proofs"]]
+        defects_for = [d for d in self.PROOF_DEFECTS if curve == "bls12_381" or d != "outside subgroup"]
+
+        def spoiled(blob, kind, avoid=()):
+            """-> (the blob with one element of the kind made bad, the element's name) or None where the proof has no finite point to spoil"""
+            blob = bytearray(blob)
+            finite = [i for i in range(13) if not blob[point_at(i) + nb - 1] & 0x40 and ("point", i) not in avoid]
+            if kind in ("flipped sign", "no point", "outside subgroup", "non-canonical infinity"):
+                if not finite:
+                    return None
+                i = finite[int(rs.randint(0, len(finite)))]
+                at = point_at(i)
+                if kind == "flipped sign":
+                    blob[at + nb - 1] ^= 0x80
+                elif kind == "no point":
+                    blob[at:at + nb] = pool["no_point"].to_bytes(nb, "little")
+                elif kind == "outside subgroup":
+                    blob[at:at + nb] = R.g1_encode(curve, pool["outside"][int(rs.randint(0, len(pool["outside"])))])
+                else:
+                    blob[at + nb - 1] = (blob[at + nb - 1] & 0x3F) | 0x40
+                    blob[at] |= 1                                     # the x of the finite point may be all zero bytes but for this one
+                return bytes(blob), ("point", i)
+            if kind == "scalar >= r":
+                free = [j for j in range(10) if ("scalar", j) not in avoid]
+                j = free[int(rs.randint(0, len(free)))]
+                big = r if rs.rand() < 0.3 else r + self.big(2 ** 256 - r)
+                blob[eval_at(j):eval_at(j) + 32] = big.to_bytes(32, "little")
+                return bytes(blob), ("scalar", j)
+            f = int(rs.randint(0, 4))
+            at = (0, 8 + 6 * nb, evals, evals + 8 + 160)[f]
+            blob[at:at + 8] = int(rs.choice([0, 4, 6, 1 << 32])).to_bytes(8, "little") if f < 3 else int(rs.choice([0, 3, 5, 1 << 32])).to_bytes(8, "little")
+            return bytes(blob), ("prefix", f)
+
+        blobs, kinds = [], []
+        clean = rs.rand() < 0.15                                      # a batch without a defect now and then
+        for _ in range(K):
+            blob = honest[int(rs.randint(0, len(honest)))]
+            kind = "none" if clean or rs.rand() < 0.3 else defects_for[int(rs.randint(1, len(defects_for)))]
+            if kind == "two bad elements":
+                a, b = (defects_for[2:-1][int(i)] for i in rs.permutation(len(defects_for) - 3)[:2])
+                one = spoiled(blob, a)
+                two = spoiled(one[0], b, avoid=(one[1],)) if one else None
+                got = (two[0], (a, one[1], b, two[1])) if two else None
+            elif kind == "none":
+                got = (blob, None)
+            else:
+                got = spoiled(blob, kind)
+            if got is None:
+                kind, got = "none", (blob, None)
+            blobs.append(got[0])
+            kinds.append(kind)
+        info.update(defects=kinds)
+        decoded = [self.proof_ref_decode(bl) for bl in blobs]
+        want_st = [st for _, st in decoded]
+        want_recs = np.stack([VF.proof_record(curve, p) for p, _ in decoded])
+        expect = dict(none=lambda s: s == 0, **{"flipped sign": lambda s: s == 0, "no point": lambda s: s == 1, "outside subgroup": lambda s: s == 2,
+                                                "scalar >= r": lambda s: s == 8, "non-canonical infinity": lambda s: s == 8,
+                                                "length prefix": lambda s: s == 16, "two bad elements": lambda s: s != 0})
+        if not all(expect[k](s) for k, s in zip(kinds, want_st)):     # the generator's own promise about the reference
+            info.update(what="the reference's status is not the defect's", status=want_st)
+            return False, info
+        d_recs, status = CD.proofs_from_bytes_dev(self.w, blobs)
+        try:
+            recs = d_recs.download(want_recs.shape)
+        finally:
+            d_recs.free()
+        info.update(what="decode status", status=want_st)
+        ok = [int(s) for s in status] == want_st
+        if ok:
+            info["what"] = "records"
+            ok = np.array_equal(recs, want_recs)
+        if ok:                                                        # the reference verifier, once per distinct blob that decodes
+            cv = B.CURVES[curve]
+            verdicts = self.codec_pool().setdefault("verdicts", {})
+            want = []
+            for bl, (proof, st) in zip(blobs, decoded):
+                key = (pr["seed"], pr["log_n"], pr["num_inputs"], tau, bl)
+                if st == 0 and key not in verdicts:
+                    try:
+                        V.verify(cv, vk, pub0, proof, tau, challenges=V.derive_challenges(PlonkTranscript(curve), vk, list(pub0), proof))
+                        verdicts[key] = True
+                    except V.VerificationError as ex:
+                        if "rejected" not in str(ex):
+                            info.update(what="reference", error=str(ex)[:120])
+                            return False, info
+                        verdicts[key] = False
+                want.append(st == 0 and verdicts[key])
+            info.update(what="verdict", want=want)
+            pub_bytes = b"".join(TR.serialize_fr(curve, x) for x in pub0)
+            stats = {}
+            got = VF.batch_verify_bytes(self.w, vk, VF.OpenKey.from_trapdoor(curve, tau), [pub_bytes] * K, blobs, seed=self.seed(), stats=stats)
+            ok = got == want and stats["decode_status"] == want_st and all(want[i] for i, k in enumerate(kinds) if k == "none") \
+                and not any(want[i] for i, k in enumerate(kinds) if k != "none")
+        for k in kinds:
+            self.hit("proof_bytes.defect." + k)
+        self.hit("proof_bytes.K.1" if K == 1 else "proof_bytes.K.>1")
+        if all(k == "none" for k in kinds):
+            self.hit("proof_bytes.all good")
+        elif "none" in kinds:
+            self.hit("proof_bytes.mixed batch")
+        return bool(ok), info
+
+    WIRE_OPS = ["sponge_stream", "elgamal", "wire_gadgets", "codec", "proof_bytes"]
+    OPS = CORE_OPS + CIRCUIT_OPS + CURVE_OPS + WIRE_OPS
+    GROUPS = {"core": CORE_OPS, "circuit": CIRCUIT_OPS, "curve": CURVE_OPS, "wire": WIRE_OPS}
 
     def close(self):
         for built in self.membership_built.values():
@@ -1825,8 +2714,9 @@ class Fuzz:
 
 def parse_ops(spec):
     """--ops: operation names and the groups "core" (the MSM / NTT / prover side, nineteen operations), "circuit" (circuits, witnesses,
-    Rescue trees, the verifier) and "curve" (the embedded Edwards curve, signatures, point gadgets, schedule replay) -> the list that every
-    draw indexes, in the order given, duplicates dropped"""
+    Rescue trees, the verifier), "curve" (the embedded Edwards curve, signatures, point gadgets, schedule replay) and "wire" (the Rescue
+    sponge and stream, ElGamal, their gadgets, the byte codec, verification from bytes) -> the list that every draw indexes, in the order
+    given, duplicates dropped"""
     names = []
     for part in (x.strip() for x in spec.split(",")):
         for name in Fuzz.GROUPS.get(part, [part]):
@@ -1861,6 +2751,8 @@ def run(seconds, seed, curves, max_log, only=None, max_ops=None, verbose=True, o
     if verbose:
         branches = {}
         for f in fz:
+            if len(fz) > 1 and f.branches:                            # a branch that only one curve can take is read from that curve's own line
+                print(f"branches on {f.curve} {dict(sorted(f.branches.items()))}", flush=True)
             for name, hits in f.branches.items():
                 branches[name] = branches.get(name, 0) + hits
         print(f"fuzz ok: {it} operations, no mismatch; per op {counts}; branches {dict(sorted(branches.items()))}", flush=True)
@@ -1874,7 +2766,7 @@ if __name__ == "__main__":
     ap.add_argument("--curve", default="both", choices=["bn254", "bls12_381", "both"])
     ap.add_argument("--max-log", type=int, default=13)
     ap.add_argument("--only", default=None, choices=Fuzz.OPS)
-    ap.add_argument("--ops", default=None, help="comma-separated operation names and groups (core, circuit, curve) to draw from; default: all")
+    ap.add_argument("--ops", default=None, help="comma-separated operation names and groups (core, circuit, curve, wire) to draw from; default: all")
     ap.add_argument("--max-ops", type=int, default=None)
     ap.add_argument("--trace", action="store_true", help="print every operation and its parameters as it finishes")
     a = ap.parse_args()
