@@ -135,6 +135,9 @@ SIGNATURES = {
     "plonk_pairing_check": (C.c_int, [C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "plonk_verify_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(VerifyKey), C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
+    "plonk_verify_batch_multi_dev": (C.c_int, [C.c_void_p, C.POINTER(VerifyKey), C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "plonk_g1_sum_tree_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "plonk_g1_from_bytes_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "plonk_g1_to_bytes_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t]),
     "plonk_fr_from_bytes_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),

@@ -98,6 +98,9 @@ struct plonk_ctx {
     uint32_t* d_replay_seg = nullptr;           // segment starts of the solve schedule as last uploaded (plonk_circuit_replay_dev), and their host copy
     size_t replay_seg_cap = 0;                  // words allocated
     std::vector<uint32_t> h_replay_seg;
+    void* d_vk_table = nullptr;                 // key table of plonk_verify_batch_multi_dev as last uploaded, and the host bytes it was uploaded from
+    size_t vk_table_cap = 0;                    // bytes allocated
+    std::vector<uint8_t> h_vk_table;
 };
 
 // state of the collective order check (comm_order_check, further down)
@@ -225,6 +228,7 @@ extern "C" void plonk_destroy(plonk_ctx* ctx) {
     if (ctx->d_rescue) (void)hipFree(ctx->d_rescue);
     if (ctx->d_edwards_table) (void)hipFree(ctx->d_edwards_table);
     if (ctx->d_replay_seg) (void)hipFree(ctx->d_replay_seg);
+    if (ctx->d_vk_table) (void)hipFree(ctx->d_vk_table);
     if (ctx->d_scratch)(void)hipFree(ctx->d_scratch);
     if (ctx->d_scratch2) (void)hipFree(ctx->d_scratch2);
     msm_ws_release(ctx->msm_ws);
@@ -1660,22 +1664,17 @@ extern "C" int plonk_pairing_check(int curve, size_t k, const uint64_t* g1_xy, c
     return plonk_fail(PLONK_ERR_ARG, "plonk_pairing_check: unknown curve %d", curve);
 }
 
-extern "C" int plonk_verify_batch_dev(plonk_ctx* ctx, const plonk_verify_key* vk, size_t k, const void* d_proofs, const void* d_pub_inputs, const void* d_rho,
-                                      void* d_out_points, void* d_status, void* d_debug) {
-    CHECK_CTX(ctx);
-    if (!vk || !vk->d_comms) return plonk_fail(PLONK_ERR_ARG, "plonk_verify_batch_dev: null verifying key");
-    if (k == 0) return PLONK_OK;
-    if (k > (1u << 22)) return plonk_fail(PLONK_ERR_ARG, "plonk_verify_batch_dev: %zu proofs (at most 2^22 per call)", k);
-    if (!d_proofs || !d_rho || !d_out_points || !d_status || (vk->num_inputs && !d_pub_inputs))
-        return plonk_fail(PLONK_ERR_ARG, "plonk_verify_batch_dev: null device buffer");
+// What the verifier kernels need of one verifying key beside its fields: log2 n, the n-th root of unity and n as a residue.  `who` names the
+// entry point and, for the multi-key one, the key ("plonk_verify_batch_multi_dev: key 3").
+static int verify_key_derive(const plonk_ctx* ctx, const plonk_verify_key* vk, const char* who, int* log_n_out, Fr* omega, Fr* n_fr_out) {
     const int log_n = ilog2_exact(vk->domain_size);
-    if (log_n < 1) return plonk_fail(PLONK_ERR_DOMAIN, "plonk_verify_batch_dev: domain size %llu is not a power of two >= 2", (unsigned long long)vk->domain_size);
+    if (log_n < 1) return plonk_fail(PLONK_ERR_DOMAIN, "%s: domain size %llu is not a power of two >= 2", who, (unsigned long long)vk->domain_size);
     if (log_n > (ctx->curve == PLONK_BN254 ? BN254_FR_TWO_ADICITY : BLS12_381_FR_TWO_ADICITY))
-        return plonk_fail(PLONK_ERR_DOMAIN, "plonk_verify_batch_dev: 2^%d exceeds the two-adicity", log_n);
-    if (vk->num_inputs > vk->domain_size) return plonk_fail(PLONK_ERR_ARG, "plonk_verify_batch_dev: %llu public inputs for %llu gates",
+        return plonk_fail(PLONK_ERR_DOMAIN, "%s: 2^%d exceeds the two-adicity", who, log_n);
+    if (vk->num_inputs > vk->domain_size) return plonk_fail(PLONK_ERR_ARG, "%s: %llu public inputs for %llu gates", who,
                                                             (unsigned long long)vk->num_inputs, (unsigned long long)vk->domain_size);
     if (vk->transcript_pos[0] >= 166 || vk->transcript_pos[1] > 166 || vk->transcript_pos[2] > 63)
-        return plonk_fail(PLONK_ERR_ARG, "plonk_verify_batch_dev: transcript position outside the STROBE rate");
+        return plonk_fail(PLONK_ERR_ARG, "%s: transcript position outside the STROBE rate", who);
     const bool bn = ctx->curve == PLONK_BN254;
     const FpParams<8>& R = bn ? BN254_FR_PARAMS : BLS12_381_FR_PARAMS;
     const int two_adicity = bn ? BN254_FR_TWO_ADICITY : BLS12_381_FR_TWO_ADICITY;
@@ -1684,19 +1683,102 @@ extern "C" int plonk_verify_batch_dev(plonk_ctx* ctx, const plonk_verify_key* vk
         const uint32_t* w = (const uint32_t*)vk->k[i];
         for (int j = 7; j >= 0; j--)
             if (w[j] != R.p[j]) { lt = w[j] < R.p[j]; break; }
-        if (!lt) return plonk_fail(PLONK_ERR_ARG, "plonk_verify_batch_dev: k[%d] is not a canonical residue", i);
+        if (!lt) return plonk_fail(PLONK_ERR_ARG, "%s: k[%d] is not a canonical residue", who, i);
     }
     Fr w = fp_from_limbs<8>(bn ? BN254_FR_TWO_ADIC_ROOT_MONT : BLS12_381_FR_TWO_ADIC_ROOT_MONT);     // primitive 2^two_adicity-th root, squared down to order n
     for (int i = log_n; i < two_adicity; i++) w = fp_sqr(w, R);
     Fr n_fr = fp_zero<8>();
     n_fr.l[0] = (uint32_t)vk->domain_size;
     n_fr.l[1] = (uint32_t)(vk->domain_size >> 32);
-    n_fr = fp_to_mont(n_fr, R);
-    int rc = ensure_scratch2(ctx, verify_batch_scratch_bytes(k));
+    *log_n_out = log_n;
+    *omega = w;
+    *n_fr_out = fp_to_mont(n_fr, R);
+    return PLONK_OK;
+}
+
+extern "C" int plonk_verify_batch_dev(plonk_ctx* ctx, const plonk_verify_key* vk, size_t k, const void* d_proofs, const void* d_pub_inputs, const void* d_rho,
+                                      void* d_out_points, void* d_status, void* d_debug) {
+    CHECK_CTX(ctx);
+    if (!vk || !vk->d_comms) return plonk_fail(PLONK_ERR_ARG, "plonk_verify_batch_dev: null verifying key");
+    if (k == 0) return PLONK_OK;
+    if (k > (1u << 22)) return plonk_fail(PLONK_ERR_ARG, "plonk_verify_batch_dev: %zu proofs (at most 2^22 per call)", k);
+    if (!d_proofs || !d_rho || !d_out_points || !d_status || (vk->num_inputs && !d_pub_inputs))
+        return plonk_fail(PLONK_ERR_ARG, "plonk_verify_batch_dev: null device buffer");
+    int log_n = 0;
+    Fr w, n_fr;
+    int rc = verify_key_derive(ctx, vk, "plonk_verify_batch_dev", &log_n, &w, &n_fr);
+    if (rc) return rc;
+    rc = ensure_scratch2(ctx, verify_batch_scratch_bytes(k));
     if (rc) return rc;
     HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
     rc = verify_batch_run(ctx->curve, vk->transcript_state, vk->transcript_pos, (size_t)log_n, (size_t)vk->num_inputs, &vk->k[0][0], w, n_fr, d_proofs,
                           vk->d_comms, d_pub_inputs, d_rho, k, d_out_points, d_status, d_debug, ctx->d_scratch2, ctx->stream);
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    ctx->ev_valid = true;
+    return rc;
+}
+
+// The key table of plonk_verify_batch_multi_dev in the context's device buffer: uploaded when its bytes differ from the last upload, from
+// the context's own host copy, ordered on the stream behind the kernels that read the previous table.
+static int verify_key_table(plonk_ctx* ctx, std::vector<uint8_t>& table) {
+    if (ctx->d_vk_table && ctx->h_vk_table == table) return PLONK_OK;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));          // earlier launches read the buffer, an earlier upload may still read the host copy
+    ctx->h_vk_table.clear();
+    if (ctx->vk_table_cap < table.size()) {
+        if (ctx->d_vk_table) (void)hipFree(ctx->d_vk_table);
+        ctx->d_vk_table = nullptr; ctx->vk_table_cap = 0;
+        HIP_TRY(hipMalloc(&ctx->d_vk_table, table.size()));
+        ctx->vk_table_cap = table.size();
+    }
+    ctx->h_vk_table.swap(table);
+    hipError_t e = hipMemcpyAsync(ctx->d_vk_table, ctx->h_vk_table.data(), ctx->h_vk_table.size(), hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) { ctx->h_vk_table.clear(); HIP_TRY(e); }
+    return PLONK_OK;
+}
+extern "C" int plonk_verify_batch_multi_dev(plonk_ctx* ctx, const plonk_verify_key* vks, size_t n_vks, size_t k, const void* d_proofs, const void* d_vk_index,
+                                            const void* d_pub_inputs, const void* d_pub_offsets, size_t pub_total, const void* d_rho, void* d_out_points,
+                                            void* d_status, void* d_debug) {
+    const char* who = "plonk_verify_batch_multi_dev";
+    CHECK_CTX(ctx);
+    if (!vks) return plonk_fail(PLONK_ERR_ARG, "%s: null verifying keys", who);
+    if (n_vks < 1 || n_vks > 4096) return plonk_fail(PLONK_ERR_ARG, "%s: %zu verifying keys (1 .. 4096 per call)", who, n_vks);
+    const size_t eb = verify_key_entry_bytes();
+    std::vector<uint8_t> table(n_vks * eb);
+    for (size_t i = 0; i < n_vks; i++) {
+        char name[64];
+        snprintf(name, sizeof name, "%s: key %zu", who, i);
+        if (!vks[i].d_comms) return plonk_fail(PLONK_ERR_ARG, "%s: null verifying key", name);
+        int log_n = 0;
+        Fr w, n_fr;
+        int rc = verify_key_derive(ctx, &vks[i], name, &log_n, &w, &n_fr);
+        if (rc) return rc;
+        if (vks[i].num_inputs > 0xFFFFFFFFull) return plonk_fail(PLONK_ERR_ARG, "%s: %llu public inputs", name, (unsigned long long)vks[i].num_inputs);
+        verify_key_entry_fill(table.data() + i * eb, vks[i].transcript_state, vks[i].transcript_pos, (size_t)log_n, (size_t)vks[i].num_inputs, &vks[i].k[0][0], w,
+                              n_fr, vks[i].d_comms);
+    }
+    if (k == 0) return PLONK_OK;
+    if (k > (1u << 22)) return plonk_fail(PLONK_ERR_ARG, "%s: %zu proofs (at most 2^22 per call)", who, k);
+    if (!d_proofs || !d_vk_index || !d_pub_offsets || !d_rho || !d_out_points || !d_status || (pub_total && !d_pub_inputs))
+        return plonk_fail(PLONK_ERR_ARG, "%s: null device buffer", who);
+    int rc = verify_key_table(ctx, table);
+    if (rc) return rc;
+    rc = ensure_scratch2(ctx, verify_batch_scratch_bytes(k));
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    rc = verify_batch_multi_run(ctx->curve, ctx->d_vk_table, n_vks, d_proofs, d_vk_index, d_pub_inputs, d_pub_offsets, pub_total, d_rho, k, d_out_points,
+                                d_status, d_debug, ctx->d_scratch2, ctx->stream);
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    ctx->ev_valid = true;
+    return rc;
+}
+extern "C" int plonk_g1_sum_tree_dev(plonk_ctx* ctx, const void* d_points, size_t k, const void* d_mask, void* d_tree) {
+    CHECK_CTX(ctx);
+    if (k == 0) return PLONK_OK;
+    if (k > (1u << 22)) return plonk_fail(PLONK_ERR_ARG, "plonk_g1_sum_tree_dev: %zu pairs (at most 2^22 per call)", k);
+    if (!d_points) return plonk_fail(PLONK_ERR_ARG, "plonk_g1_sum_tree_dev: d_points is null");
+    if (!d_tree) return plonk_fail(PLONK_ERR_ARG, "plonk_g1_sum_tree_dev: d_tree is null");
+    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    const int rc = g1_sum_tree_run(ctx->curve, d_points, k, d_mask, d_tree, ctx->stream);
     HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
     ctx->ev_valid = true;
     return rc;

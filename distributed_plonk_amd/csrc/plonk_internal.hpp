@@ -233,6 +233,17 @@ size_t verify_batch_scratch_bytes(size_t k);
 int verify_batch_run(int curve, const uint8_t* strobe, const uint32_t* strobe_pos3, size_t log_n, size_t num_inputs, const uint64_t* k_mont,
                      const Fr& omega, const Fr& n_fr, const void* d_proofs, const void* d_vk_pts, const void* d_pub, const void* d_rho, size_t k,
                      void* d_out, void* d_status, void* d_debug, void* scratch, hipStream_t stream);
+// the same with a key per proof.  The key table is verify_key_entry_bytes() per key, each row written by verify_key_entry_fill on the host
+// (every byte of it, so that tables compare with memcmp) and uploaded by the caller; d_vk_index k u32, d_pub_off k + 1 u64 into d_pub.
+size_t verify_key_entry_bytes();
+void verify_key_entry_fill(void* entry, const uint8_t* strobe, const uint32_t* strobe_pos3, size_t log_n, size_t num_inputs, const uint64_t* k_mont,
+                           const Fr& omega, const Fr& n_fr, const void* d_comms);
+int verify_batch_multi_run(int curve, const void* d_key_table, size_t n_vks, const void* d_proofs, const void* d_vk_index, const void* d_pub,
+                           const void* d_pub_off, size_t pub_total, const void* d_rho, size_t k, void* d_out, void* d_status, void* d_debug, void* scratch,
+                           hipStream_t stream);
+// k pairs of affine points (a non-zero mask word reads as two infinities) -> the heap-ordered tree of pairwise sums, 2P - 1 pairs for P the
+// next power of two >= k: one launch for the leaves, one per level above them.  Enqueued only.
+int g1_sum_tree_run(int curve, const void* d_points, size_t k, const void* d_mask, void* d_tree, hipStream_t stream);
 // ark-serialize bytes <-> Montgomery limbs (codec_kernels.hpp, built in synth.hip).  Element i = o * inner + j of a launch sits at
 // base + o * stride + j * inner_stride on both sides (bytes on the byte side, u64 on the limb side) and reports into status[o * status_stride];
 // base pointers already carry the offset of element 0.  Status words are OR-ed into, never cleared, except by codec_proofs_run.  Enqueued only.

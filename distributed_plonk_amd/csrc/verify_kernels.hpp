@@ -8,7 +8,13 @@
 //   A = W_z + u W_zw,   B = zeta W_z + u zeta w W_zw + F + u [z] - (E + u z_w) G,
 //   F = [r] + sum_{i<5} v^(1+i) [w_i] + sum_{i<4} v^(6+i) [sigma_i],   [r] the linearisation over the 13 selectors, [z], [sigma_4], [t_i].
 // A proof whose status word is not 0 gets A = B = O.  The pairing of the sums runs on the host (pairing.hpp).
+// verify_scalars_multi_kernel / verify_points_multi_kernel do the same with a key PER PROOF (jf-plonk's batch_verify): the keys' Params and
+// commitment pointers sit in one device table, lane j works under row vk_index[j] on its span of a ragged public-input list.  They share
+// the lane bodies (vfy::scalars_lane, vfy::points_lane) with the one-key kernels, which stay what they were.
+// g1_tree_leaves_kernel / g1_tree_level_kernel fold the K output pairs into a heap-ordered sum tree, so that the host pairs the root and,
+// when that fails, bisects over nodes it reads back instead of re-adding points.
 #pragma once
+#include <cstring>
 #include "constants.h"
 #include "ec.hpp"
 
@@ -21,13 +27,18 @@ constexpr int NDEBUG = 9;                // beta, gamma, alpha, zeta, v, u, PI(z
 constexpr int STROBE_R = 166;
 constexpr int LANES = 64;                // lanes per workgroup of the transcript kernel: 64 x 200 B of LDS
 
-enum : uint32_t { ST_OFF_CURVE = 1, ST_SUBGROUP = 2, ST_ZETA_DOMAIN = 4, ST_NONCANONICAL = 8 };
+enum : uint32_t { ST_OFF_CURVE = 1, ST_SUBGROUP = 2, ST_ZETA_DOMAIN = 4, ST_NONCANONICAL = 8,
+                  ST_BAD_KEY = 32, ST_BAD_SPAN = 64 };     // the multi-key kernels only (16 is the codec's)
 
 struct Params {
     uint8_t strobe[200];                 // the transcript after the verifying-key messages
     uint32_t pos, pos_begin, cur_flags;
     uint32_t log_n, num_inputs;
     Fr k[5], omega, n_fr;                // Montgomery
+};
+struct KeyEntry {                        // one row of the key table of the multi-key kernels
+    Params prm;
+    const uint32_t* comms;               // device: 13 selector then 5 sigma commitments
 };
 
 template <int N> __device__ __forceinline__ bool lt_mod(const uint32_t* a, const uint32_t* p) {     // a < p as integers
@@ -175,18 +186,14 @@ template <int NQ> __device__ __forceinline__ AffPt<NQ> load_pt(const uint32_t* r
 }  // namespace vfy
 
 // ------------------------------------------------------------------------------------------------ kernel 1: checks, transcript, scalars
-// (kernels at global scope, like every other kernel of the library: codehash.py keys the machine code by kernel name)
+namespace vfy {
+// One proof under one key: prm is that key's entry (a kernel argument of verify_scalars_kernel, a row of the key table of
+// verify_scalars_multi_kernel), st the lane's 200 bytes of LDS already holding prm.strobe, rec the proof's record, pub ITS public inputs
+// (prm.num_inputs of them).  No barrier: a lane that returns early leaves its neighbours alone.
 template <int NQ>
-__global__ void __launch_bounds__(vfy::LANES) verify_scalars_kernel(const vfy::Params prm, const uint32_t* __restrict__ proofs, const Fr* __restrict__ pub,
-                                                               const Fr* __restrict__ rho, uint32_t k, Fr* __restrict__ coef, uint32_t* __restrict__ status,
-                                                               Fr* __restrict__ debug, const FpParams<8> R, const FpParams<NQ> Q, const Fp<NQ> b) {
-    using namespace vfy;
-    __shared__ __attribute__((aligned(8))) uint8_t lds[LANES * 200];
-    const uint32_t pid = blockIdx.x * LANES + threadIdx.x;
-    uint8_t* st = lds + threadIdx.x * 200;
-    for (int i = 0; i < 200; i++) st[i] = prm.strobe[i];
-    if (pid >= k) return;
-    const uint32_t* rec = proofs + (size_t)pid * (2 * NQ * NPTS + 8 * NEVALS);
+__device__ __forceinline__ void scalars_lane(const Params& prm, uint8_t* st, const uint32_t* rec, const Fr* pub, const Fr* __restrict__ rho, uint32_t pid,
+                                             Fr* __restrict__ coef, uint32_t* __restrict__ status, Fr* __restrict__ debug, const FpParams<8>& R,
+                                             const FpParams<NQ>& Q, const Fp<NQ>& b) {
     const Fr* ev = reinterpret_cast<const Fr*>(rec + 2 * NQ * NPTS);
     uint32_t stw = 0;
     // input checks: coordinates and evaluations canonical, points on the curve (or (0, 0) = infinity)
@@ -200,7 +207,7 @@ __global__ void __launch_bounds__(vfy::LANES) verify_scalars_kernel(const vfy::P
     for (int i = 0; i < NEVALS; i++)
         if (!lt_mod<8>(ev[i].l, R.p)) stw |= ST_NONCANONICAL;
     for (uint32_t i = 0; i < prm.num_inputs; i++)
-        if (!lt_mod<8>(pub[(size_t)pid * prm.num_inputs + i].l, R.p)) stw |= ST_NONCANONICAL;
+        if (!lt_mod<8>(pub[i].l, R.p)) stw |= ST_NONCANONICAL;
     if (!lt_mod<8>(rho[pid].l, R.p)) stw |= ST_NONCANONICAL;
     Fr* cf = coef + (size_t)pid * NCOEF;
     if (stw) {
@@ -210,7 +217,7 @@ __global__ void __launch_bounds__(vfy::LANES) verify_scalars_kernel(const vfy::P
 
     // Fiat-Shamir (verifier_ref.derive_challenges), continuing from the verifying-key state
     Strobe t{st, (int)prm.pos, (int)prm.pos_begin, (int)prm.cur_flags};
-    for (uint32_t i = 0; i < prm.num_inputs; i++) append_fr(t, "public input", fp_from_mont(pub[(size_t)pid * prm.num_inputs + i], R));
+    for (uint32_t i = 0; i < prm.num_inputs; i++) append_fr(t, "public input", fp_from_mont(pub[i], R));
     for (int i = 0; i < 5; i++) append_g1<NQ>(t, "witness_poly_comms", load_pt<NQ>(rec, i), Q);
     const Fr beta = challenge(t, "beta", R);
     const Fr gamma = challenge(t, "gamma", R);
@@ -238,7 +245,7 @@ __global__ void __launch_bounds__(vfy::LANES) verify_scalars_kernel(const vfy::P
     Fr num = fp_zero<8>(), den = one, wi = one;
     for (uint32_t i = 0; i < prm.num_inputs; i++) {
         const Fr d = fp_sub(zeta, wi, R);
-        num = fp_add(fp_mul(num, d, R), fp_mul(fp_mul(pub[(size_t)pid * prm.num_inputs + i], wi, R), den, R), R);
+        num = fp_add(fp_mul(num, d, R), fp_mul(fp_mul(pub[i], wi, R), den, R), R);
         den = fp_mul(den, d, R);
         wi = fp_mul(wi, prm.omega, R);
     }
@@ -293,6 +300,53 @@ __global__ void __launch_bounds__(vfy::LANES) verify_scalars_kernel(const vfy::P
         dbg[6] = pi; dbg[7] = r_zeta; dbg[8] = E;
     }
 }
+}  // namespace vfy
+
+// (kernels at global scope, like every other kernel of the library: codehash.py keys the machine code by kernel name)
+template <int NQ>
+__global__ void __launch_bounds__(vfy::LANES) verify_scalars_kernel(const vfy::Params prm, const uint32_t* __restrict__ proofs, const Fr* __restrict__ pub,
+                                                               const Fr* __restrict__ rho, uint32_t k, Fr* __restrict__ coef, uint32_t* __restrict__ status,
+                                                               Fr* __restrict__ debug, const FpParams<8> R, const FpParams<NQ> Q, const Fp<NQ> b) {
+    using namespace vfy;
+    __shared__ __attribute__((aligned(8))) uint8_t lds[LANES * 200];
+    const uint32_t pid = blockIdx.x * LANES + threadIdx.x;
+    uint8_t* st = lds + threadIdx.x * 200;
+    for (int i = 0; i < 200; i++) st[i] = prm.strobe[i];
+    if (pid >= k) return;
+    scalars_lane<NQ>(prm, st, proofs + (size_t)pid * (2 * NQ * NPTS + 8 * NEVALS), pub + (size_t)pid * prm.num_inputs, rho, pid, coef, status, debug, R, Q, b);
+}
+
+// The same with a key per proof: lane j works under keys[vk_index[j]] on the public inputs [pub_off[j], pub_off[j + 1]) of a ragged list.
+// Lanes of one wave may carry different log_n and num_inputs: their loops diverge, nothing else.  A lane whose index or span is bad
+// reads nothing through either — not the key table, not pub — and writes only its status word (verify_points_multi_kernel gives it (O, O)):
+//   ST_BAD_KEY   vk_index[j] >= n_vks
+//   ST_BAD_SPAN  pub_off[j] > pub_off[j + 1], pub_off[j + 1] > pub_total, or (under a good index) a length other than the key's num_inputs
+template <int NQ>
+__global__ void __launch_bounds__(vfy::LANES) verify_scalars_multi_kernel(const vfy::KeyEntry* __restrict__ keys, uint32_t n_vks,
+                                                                     const uint32_t* __restrict__ vk_index, const uint32_t* __restrict__ proofs,
+                                                                     const Fr* __restrict__ pub, const uint64_t* __restrict__ pub_off, uint64_t pub_total,
+                                                                     const Fr* __restrict__ rho, uint32_t k, Fr* __restrict__ coef,
+                                                                     uint32_t* __restrict__ status, Fr* __restrict__ debug, const FpParams<8> R,
+                                                                     const FpParams<NQ> Q, const Fp<NQ> b) {
+    using namespace vfy;
+    __shared__ __attribute__((aligned(8))) uint8_t lds[LANES * 200];
+    const uint32_t pid = blockIdx.x * LANES + threadIdx.x;
+    if (pid >= k) return;
+    const uint32_t idx = vk_index[pid];
+    const uint64_t lo = pub_off[pid], hi = pub_off[pid + 1];
+    uint32_t stw = 0;
+    if (idx >= n_vks) stw |= ST_BAD_KEY;
+    if (lo > hi || hi > pub_total) stw |= ST_BAD_SPAN;
+    else if (!stw && hi - lo != (uint64_t)keys[idx].prm.num_inputs) stw |= ST_BAD_SPAN;
+    if (stw) {
+        status[pid] = stw;
+        return;
+    }
+    const Params& prm = keys[idx].prm;
+    uint8_t* st = lds + threadIdx.x * 200;
+    for (int i = 0; i < 200; i++) st[i] = prm.strobe[i];
+    scalars_lane<NQ>(prm, st, proofs + (size_t)pid * (2 * NQ * NPTS + 8 * NEVALS), pub + lo, rho, pid, coef, status, debug, R, Q, b);
+}
 
 // ------------------------------------------------------------------------------------------------ kernel 2: r-subgroup of G1 (BLS12-381)
 // (the loop below has a copy, codec::g1_times_r_is_inf in codec_kernels.hpp, kept apart so that this kernel's machine code stays what the
@@ -323,21 +377,14 @@ template <int NQ> __device__ __forceinline__ AffPt<NQ> term_point(int j, const u
     if (j < 30) return load_pt<NQ>(rec, j - 19);              // wires, z, quotient chunks
     return load_pt<NQ>(rec, j >= 32 ? j - 21 : j - 19);       // W_z, W_zw (B: 30, 31; A: 32, 33)
 }
-}  // namespace vfy
-
+// one output point: which = 0 rho B over the 32 points of slots 0..31, which = 1 rho A over slots 32, 33; (0, 0) for a proof that is not ok
 template <int NQ>
-__global__ void __launch_bounds__(64) verify_points_kernel(const uint32_t* __restrict__ proofs, const uint32_t* __restrict__ vk, uint32_t k,
-                                                            const Fr* __restrict__ coef, const uint32_t* __restrict__ status, uint32_t* __restrict__ out,
-                                                            const FpParams<NQ> Q, const AffPt<NQ> g) {
-    using namespace vfy;
-    const uint32_t gid = blockIdx.x * 64 + threadIdx.x;
-    if (gid >= 2 * k) return;
-    const uint32_t pid = gid >> 1, which = gid & 1;            // 0: rho B, 1: rho A
-    uint32_t* o = out + (size_t)gid * 2 * NQ;
+__device__ __forceinline__ void points_lane(uint32_t pid, uint32_t which, bool ok, const uint32_t* __restrict__ proofs, const uint32_t* vk,
+                                            const Fr* __restrict__ coef, uint32_t* o, const FpParams<NQ>& Q, const AffPt<NQ>& g) {
     AffPt<NQ> res;
     res.x = fp_zero<NQ>();
     res.y = fp_zero<NQ>();
-    if (status[pid] == 0) {
+    if (ok) {
         const uint32_t* rec = proofs + (size_t)pid * (2 * NQ * NPTS + 8 * NEVALS);
         const Fr* cf = coef + (size_t)pid * NCOEF;
         const int j0 = which ? 32 : 0, j1 = which ? 34 : 32;
@@ -353,6 +400,63 @@ __global__ void __launch_bounds__(64) verify_points_kernel(const uint32_t* __res
     for (int i = 0; i < NQ; i++) {
         o[i] = res.x.l[i];
         o[NQ + i] = res.y.l[i];
+    }
+}
+}  // namespace vfy
+
+template <int NQ>
+__global__ void __launch_bounds__(64) verify_points_kernel(const uint32_t* __restrict__ proofs, const uint32_t* __restrict__ vk, uint32_t k,
+                                                            const Fr* __restrict__ coef, const uint32_t* __restrict__ status, uint32_t* __restrict__ out,
+                                                            const FpParams<NQ> Q, const AffPt<NQ> g) {
+    const uint32_t gid = blockIdx.x * 64 + threadIdx.x;
+    if (gid >= 2 * k) return;
+    const uint32_t pid = gid >> 1;                             // gid & 1: 0 rho B, 1 rho A
+    vfy::points_lane<NQ>(pid, gid & 1, status[pid] == 0, proofs, vk, coef, out + (size_t)gid * 2 * NQ, Q, g);
+}
+
+// the key points through the proof's table row; a status of 0 says that verify_scalars_multi_kernel found vk_index[pid] < n_vks
+template <int NQ>
+__global__ void __launch_bounds__(64) verify_points_multi_kernel(const uint32_t* __restrict__ proofs, const vfy::KeyEntry* __restrict__ keys,
+                                                                  const uint32_t* __restrict__ vk_index, uint32_t k, const Fr* __restrict__ coef,
+                                                                  const uint32_t* __restrict__ status, uint32_t* __restrict__ out, const FpParams<NQ> Q,
+                                                                  const AffPt<NQ> g) {
+    const uint32_t gid = blockIdx.x * 64 + threadIdx.x;
+    if (gid >= 2 * k) return;
+    const uint32_t pid = gid >> 1;
+    const bool ok = status[pid] == 0;
+    vfy::points_lane<NQ>(pid, gid & 1, ok, proofs, ok ? keys[vk_index[pid]].comms : nullptr, coef, out + (size_t)gid * 2 * NQ, Q, g);
+}
+
+// ------------------------------------------------------------------------------------------------ the fold: a sum tree over the K pairs
+// d_tree: 2P - 1 pairs in heap order (P the next power of two >= k; root 0, children of i at 2i + 1 and 2i + 2, leaf j at P - 1 + j), every
+// point affine with (0, 0) = infinity.  One lane per POINT (two per pair), one launch per level.  The addition is complete: xyzz_madd
+// (ec.hpp) returns the other operand for an infinity on either side, doubles when x and y agree and gives infinity when only x does; a
+// doubling of a point with y = 0 has ZZ = 0, which xyzz_to_affine writes as (0, 0).  One inversion per node point.
+template <int NQ>
+__global__ void __launch_bounds__(64) g1_tree_leaves_kernel(const uint32_t* __restrict__ points, const uint32_t* __restrict__ mask, uint32_t k, uint32_t P,
+                                                             uint32_t* __restrict__ tree) {
+    const uint32_t gid = blockIdx.x * 64 + threadIdx.x;        // point gid & 1 of leaf gid >> 1
+    if (gid >= 2 * P) return;
+    const uint32_t j = gid >> 1;
+    const bool live = j < k && !(mask && mask[j]);
+    const uint32_t* src = points + (size_t)gid * 2 * NQ;
+    uint32_t* dst = tree + ((size_t)(P - 1) * 2 + gid) * 2 * NQ;
+#pragma unroll
+    for (int i = 0; i < 2 * NQ; i++) dst[i] = live ? src[i] : 0u;
+}
+template <int NQ>
+__global__ void __launch_bounds__(64) g1_tree_level_kernel(uint32_t* __restrict__ tree, uint32_t m, const FpParams<NQ> Q) {
+    const uint32_t gid = blockIdx.x * 64 + threadIdx.x;        // point gid & 1 of node m - 1 + (gid >> 1), the level of m nodes
+    if (gid >= 2 * m) return;
+    const size_t node = (size_t)(m - 1) + (gid >> 1), which = gid & 1;
+    const AffPt<NQ> a = vfy::load_pt<NQ>(tree + ((2 * node + 1) * 2 + which) * 2 * NQ, 0);
+    const AffPt<NQ> b = vfy::load_pt<NQ>(tree + ((2 * node + 2) * 2 + which) * 2 * NQ, 0);
+    const AffPt<NQ> r = xyzz_to_affine(xyzz_madd_cold(xyzz_from_affine(a, Q), b, Q), Q);
+    uint32_t* o = tree + (node * 2 + which) * 2 * NQ;
+#pragma unroll
+    for (int i = 0; i < NQ; i++) {
+        o[i] = r.x.l[i];
+        o[NQ + i] = r.y.l[i];
     }
 }
 
@@ -377,14 +481,40 @@ int run(const Params& prm, const void* proofs, const void* vk_pts, const void* p
     return PLONK_OK;
 }
 
-}  // namespace vfy
+template <int NQ>
+int run_multi(const KeyEntry* keys, uint32_t n_vks, const void* proofs, const void* vk_index, const void* pub, const void* pub_off, uint64_t pub_total,
+              const void* rho, uint32_t k, void* out, uint32_t* status, void* debug, void* scratch, const FpParams<8>& R, const FpParams<NQ>& Q,
+              const uint32_t* b, const uint32_t* gx, const uint32_t* gy, hipStream_t stream) {
+    Fr* coef = (Fr*)scratch;
+    const Fp<NQ> bq = fp_from_limbs<NQ>(b);
+    AffPt<NQ> g;
+    g.x = fp_from_limbs<NQ>(gx);
+    g.y = fp_from_limbs<NQ>(gy);
+    hipLaunchKernelGGL(verify_scalars_multi_kernel<NQ>, dim3((k + LANES - 1) / LANES), dim3(LANES), 0, stream, keys, n_vks, (const uint32_t*)vk_index,
+                       (const uint32_t*)proofs, (const Fr*)pub, (const uint64_t*)pub_off, pub_total, (const Fr*)rho, k, coef, status, (Fr*)debug, R, Q, bq);
+    if (NQ == 12)                                             // skips every proof whose status is already set: nothing is read for a bad index
+        hipLaunchKernelGGL(verify_subgroup_kernel<NQ>, dim3((k * NPTS + 127) / 128), dim3(128), 0, stream, (const uint32_t*)proofs, k, status, R, Q);
+    hipLaunchKernelGGL(verify_points_multi_kernel<NQ>, dim3((2 * k + 63) / 64), dim3(64), 0, stream, (const uint32_t*)proofs, keys,
+                       (const uint32_t*)vk_index, k, (const Fr*)coef, (const uint32_t*)status, (uint32_t*)out, Q, g);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return plonk_fail(PLONK_ERR_HIP, "verify_batch_multi launch: %s", hipGetErrorString(e));
+    return PLONK_OK;
+}
 
-size_t verify_batch_scratch_bytes(size_t k) { return k * vfy::NCOEF * sizeof(Fr); }
+template <int NQ> int sum_tree(const void* points, uint32_t k, const void* mask, void* tree, const FpParams<NQ>& Q, hipStream_t stream) {
+    uint32_t P = 1;
+    while (P < k) P <<= 1;
+    hipLaunchKernelGGL(g1_tree_leaves_kernel<NQ>, dim3((2 * P + 63) / 64), dim3(64), 0, stream, (const uint32_t*)points, (const uint32_t*)mask, k, P,
+                       (uint32_t*)tree);
+    for (uint32_t m = P >> 1; m >= 1; m >>= 1)
+        hipLaunchKernelGGL(g1_tree_level_kernel<NQ>, dim3((2 * m + 63) / 64), dim3(64), 0, stream, (uint32_t*)tree, m, Q);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return plonk_fail(PLONK_ERR_HIP, "g1_sum_tree launch: %s", hipGetErrorString(e));
+    return PLONK_OK;
+}
 
-int verify_batch_run(int curve, const uint8_t* strobe, const uint32_t* strobe_pos3, size_t log_n, size_t num_inputs, const uint64_t* k_mont,
-                     const Fr& omega, const Fr& n_fr, const void* d_proofs, const void* d_vk_pts, const void* d_pub, const void* d_rho, size_t k,
-                     void* d_out, void* d_status, void* d_debug, void* scratch, hipStream_t stream) {
-    vfy::Params prm;
+static void fill_params(Params& prm, const uint8_t* strobe, const uint32_t* strobe_pos3, size_t log_n, size_t num_inputs, const uint64_t* k_mont,
+                        const Fr& omega, const Fr& n_fr) {
     for (int i = 0; i < 200; i++) prm.strobe[i] = strobe[i];
     prm.pos = strobe_pos3[0];
     prm.pos_begin = strobe_pos3[1];
@@ -394,9 +524,46 @@ int verify_batch_run(int curve, const uint8_t* strobe, const uint32_t* strobe_po
     for (int i = 0; i < 5; i++) prm.k[i] = fp_from_limbs<8>((const uint32_t*)(k_mont + 4 * i));
     prm.omega = omega;
     prm.n_fr = n_fr;
+}
+
+}  // namespace vfy
+
+size_t verify_batch_scratch_bytes(size_t k) { return k * vfy::NCOEF * sizeof(Fr); }
+
+int verify_batch_run(int curve, const uint8_t* strobe, const uint32_t* strobe_pos3, size_t log_n, size_t num_inputs, const uint64_t* k_mont,
+                     const Fr& omega, const Fr& n_fr, const void* d_proofs, const void* d_vk_pts, const void* d_pub, const void* d_rho, size_t k,
+                     void* d_out, void* d_status, void* d_debug, void* scratch, hipStream_t stream) {
+    vfy::Params prm;
+    vfy::fill_params(prm, strobe, strobe_pos3, log_n, num_inputs, k_mont, omega, n_fr);
     if (curve == PLONK_BN254)
         return vfy::run<8>(prm, d_proofs, d_vk_pts, d_pub, d_rho, (uint32_t)k, d_out, (uint32_t*)d_status, d_debug, scratch, BN254_FR_PARAMS, BN254_FQ_PARAMS,
                            BN254_G1_B_MONT, BN254_G1_GX_MONT, BN254_G1_GY_MONT, stream);
     return vfy::run<12>(prm, d_proofs, d_vk_pts, d_pub, d_rho, (uint32_t)k, d_out, (uint32_t*)d_status, d_debug, scratch, BLS12_381_FR_PARAMS,
                         BLS12_381_FQ_PARAMS, BLS12_381_G1_B_MONT, BLS12_381_G1_GX_MONT, BLS12_381_G1_GY_MONT, stream);
+}
+
+size_t verify_key_entry_bytes() { return sizeof(vfy::KeyEntry); }
+
+void verify_key_entry_fill(void* entry, const uint8_t* strobe, const uint32_t* strobe_pos3, size_t log_n, size_t num_inputs, const uint64_t* k_mont,
+                           const Fr& omega, const Fr& n_fr, const void* d_comms) {
+    vfy::KeyEntry* e = (vfy::KeyEntry*)entry;
+    memset(e, 0, sizeof *e);                                  // padding too: the context compares tables as bytes
+    vfy::fill_params(e->prm, strobe, strobe_pos3, log_n, num_inputs, k_mont, omega, n_fr);
+    e->comms = (const uint32_t*)d_comms;
+}
+
+int verify_batch_multi_run(int curve, const void* d_key_table, size_t n_vks, const void* d_proofs, const void* d_vk_index, const void* d_pub,
+                           const void* d_pub_off, size_t pub_total, const void* d_rho, size_t k, void* d_out, void* d_status, void* d_debug, void* scratch,
+                           hipStream_t stream) {
+    const vfy::KeyEntry* keys = (const vfy::KeyEntry*)d_key_table;
+    if (curve == PLONK_BN254)
+        return vfy::run_multi<8>(keys, (uint32_t)n_vks, d_proofs, d_vk_index, d_pub, d_pub_off, pub_total, d_rho, (uint32_t)k, d_out, (uint32_t*)d_status, d_debug,
+                                 scratch, BN254_FR_PARAMS, BN254_FQ_PARAMS, BN254_G1_B_MONT, BN254_G1_GX_MONT, BN254_G1_GY_MONT, stream);
+    return vfy::run_multi<12>(keys, (uint32_t)n_vks, d_proofs, d_vk_index, d_pub, d_pub_off, pub_total, d_rho, (uint32_t)k, d_out, (uint32_t*)d_status, d_debug,
+                              scratch, BLS12_381_FR_PARAMS, BLS12_381_FQ_PARAMS, BLS12_381_G1_B_MONT, BLS12_381_G1_GX_MONT, BLS12_381_G1_GY_MONT, stream);
+}
+
+int g1_sum_tree_run(int curve, const void* d_points, size_t k, const void* d_mask, void* d_tree, hipStream_t stream) {
+    if (curve == PLONK_BN254) return vfy::sum_tree<8>(d_points, (uint32_t)k, d_mask, d_tree, BN254_FQ_PARAMS, stream);
+    return vfy::sum_tree<12>(d_points, (uint32_t)k, d_mask, d_tree, BLS12_381_FQ_PARAMS, stream);
 }

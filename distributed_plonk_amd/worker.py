@@ -541,6 +541,18 @@ class PlonkWorker:
         """k serialized proofs -> k records of plonk_verify_batch_dev and k status words (plonk_proofs_from_bytes_dev).  Enqueued, not synchronised."""
         check(self.lib.plonk_proofs_from_bytes_dev(self.ctx, d_bytes or None, k, d_proofs or None, d_status or None))
 
+    def verify_batch_multi_dev(self, keys, n_vks: int, k: int, d_proofs: int, d_vk_index: int, d_pub_inputs: int, d_pub_offsets: int, pub_total: int,
+                               d_rho: int, d_out_points: int, d_status: int, d_debug: int = 0):
+        """k proofs, proof j under keys[vk_index[j]] (a ctypes array of _ffi.VerifyKey) on its span of a ragged public-input list
+        (plonk_verify_batch_multi_dev).  Enqueued, not synchronised."""
+        check(self.lib.plonk_verify_batch_multi_dev(self.ctx, keys, n_vks, k, d_proofs or None, d_vk_index or None, d_pub_inputs or None,
+                                                    d_pub_offsets or None, pub_total, d_rho or None, d_out_points or None, d_status or None,
+                                                    d_debug or None))
+
+    def g1_sum_tree_dev(self, d_points: int, k: int, d_mask: int, d_tree: int):
+        """k pairs of affine points -> the heap-ordered tree of their pairwise sums (plonk_g1_sum_tree_dev).  Enqueued, not synchronised."""
+        check(self.lib.plonk_g1_sum_tree_dev(self.ctx, d_points or None, k, d_mask or None, d_tree or None))
+
     def codec_first_bad_dev(self, d_status: int, count: int, status_stride: int = 1) -> int:
         """The lowest index with a non-zero status word, -1 when there is none (plonk_codec_first_bad_dev).  Synchronises."""
         first = C.c_int64(-1)

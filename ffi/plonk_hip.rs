@@ -191,6 +191,10 @@ extern "C" {
     pub fn plonk_pairing_check(curve: c_int, k: usize, g1_xy: *const u64, g2_xy: *const u64, is_one: *mut c_int) -> c_int;
     pub fn plonk_verify_batch_dev(ctx: *mut plonk_ctx, vk: *const plonk_verify_key, k: usize, d_proofs: *const c_void, d_pub_inputs: *const c_void,
                                   d_rho: *const c_void, d_out_points: *mut c_void, d_status: *mut c_void, d_debug: *mut c_void) -> c_int;
+    pub fn plonk_verify_batch_multi_dev(ctx: *mut plonk_ctx, vks: *const plonk_verify_key, n_vks: usize, k: usize, d_proofs: *const c_void, d_vk_index: *const c_void,
+                                        d_pub_inputs: *const c_void, d_pub_offsets: *const c_void, pub_total: usize, d_rho: *const c_void, d_out_points: *mut c_void,
+                                        d_status: *mut c_void, d_debug: *mut c_void) -> c_int;
+    pub fn plonk_g1_sum_tree_dev(ctx: *mut plonk_ctx, d_points: *const c_void, k: usize, d_mask: *const c_void, d_tree: *mut c_void) -> c_int;
     pub fn plonk_g1_from_bytes_dev(ctx: *mut plonk_ctx, d_bytes: *const c_void, in_stride: usize, count: usize, encoding: c_int, check_subgroup: c_int, d_out_xy: *mut c_void, out_stride_u64: usize, d_status: *mut c_void, status_stride: usize) -> c_int;
     pub fn plonk_g1_to_bytes_dev(ctx: *mut plonk_ctx, d_xy: *const c_void, in_stride_u64: usize, count: usize, encoding: c_int, d_bytes: *mut c_void, out_stride: usize) -> c_int;
     pub fn plonk_fr_from_bytes_dev(ctx: *mut plonk_ctx, d_bytes: *const c_void, in_stride: usize, count: usize, d_out: *mut c_void, out_stride_u64: usize, d_status: *mut c_void, status_stride: usize) -> c_int;

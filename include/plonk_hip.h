@@ -522,6 +522,29 @@ typedef struct plonk_verify_key {
 } plonk_verify_key;
 int plonk_verify_batch_dev(plonk_ctx* ctx, const plonk_verify_key* vk, size_t k, const void* d_proofs, const void* d_pub_inputs, const void* d_rho,
                            void* d_out_points, void* d_status, void* d_debug);
+/* The same with one verifying key PER PROOF (jf-plonk's batch_verify): a block that mixes circuits, each with its own domain size and
+ * public-input count, is one call and one pairing check.
+ *   vks           HOST array of n_vks keys (1 .. 4096), each with its own d_comms, each checked as plonk_verify_batch_dev checks its key; an
+ *                 error names the key's index.  The library derives omega, n and log2 n per key and keeps them, the transcript states and
+ *                 the commitment pointers in a device table of its own (uploaded again only when a call's keys differ from the last call's)
+ *   d_proofs      k records as above: the layout does not depend on the key
+ *   d_vk_index    k u32: the key of proof j
+ *   d_pub_offsets k + 1 u64, in Fr elements into d_pub_inputs (pub_total elements; NULL allowed when pub_total is 0): proof j owns
+ *                 [off[j], off[j+1]), possibly empty
+ *   d_rho, d_out_points, d_status, d_debug as above, with two more status bits, verdicts like the others:
+ *                 | 32 the key index is >= n_vks, | 64 the span is bad: off[j] > off[j+1], off[j+1] > pub_total, or (under a good index) a
+ *                 length other than the key's num_inputs.  Such a proof reads nothing through its index or span and gets (0, 0) twice.
+ * Lanes of one wave may run under different keys; they diverge in the loops over log2 n and the public inputs only. */
+int plonk_verify_batch_multi_dev(plonk_ctx* ctx, const plonk_verify_key* vks, size_t n_vks, size_t k, const void* d_proofs, const void* d_vk_index,
+                                 const void* d_pub_inputs, const void* d_pub_offsets, size_t pub_total, const void* d_rho, void* d_out_points,
+                                 void* d_status, void* d_debug);
+/* The fold of a batch as a sum tree on the device.  d_points: k pairs [rho B, rho A] of affine G1 points with canonical coordinates
+ * (exactly d_out_points above; k <= 2^22); d_mask: NULL or k u32, a non-zero word turning its pair into two infinities (the status words).
+ * d_tree receives 2P - 1 pairs in heap order, P the next power of two >= k: the root is node 0, the children of node i are 2i + 1 and
+ * 2i + 2, leaf j is node P - 1 + j, leaves >= k are infinity, every inner node is the pair of sums of its children's pairs.  The addition
+ * is complete (equal inputs, opposite inputs — the sum is written (0, 0) —, infinity on either side or both).  One launch for the leaves
+ * and one per level, one lane per output point, one inversion per inner point; enqueued on the context's stream; k = 0 is a no-op. */
+int plonk_g1_sum_tree_dev(plonk_ctx* ctx, const void* d_points, size_t k, const void* d_mask, void* d_tree);
 /* ark-serialize 0.3 bytes <-> Montgomery limbs (`to_bytes!` of the reference; csrc/codec_kernels.hpp), one lane per element.
  * A G1Affine is, compressed, its x coordinate little-endian (32 B BN254 / 48 B BLS12-381) with two flags in the top bits of the last byte:
  * 0x80 "y is the larger of {y, -y} as integers", 0x40 infinity; uncompressed, x then y (64 B / 96 B), the last byte of y carrying only 0x40.

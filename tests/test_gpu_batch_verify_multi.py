@@ -1,0 +1,464 @@
+"""Batched verification with a verifying key PER PROOF (plonk_verify_batch_multi_dev), the device fold (plonk_g1_sum_tree_dev) and the
+Python surface over them (verifier.VerifyKeySet, batch_verify_multi, batch_verify_multi_bytes), bit for bit against oracle/verifier_ref.py
+and oracle/bigint_ref.py.  Nothing expected here comes from the device path under test.
+
+Keys: two real circuits (2^10 gates with 3 public inputs; the smallest size the prover accepts from 2^5 up with 1) and three statement-only
+keys built as test_gpu_batch_verify_edges.py builds its own (domain 2 with 2 inputs — the whole domain —, domain 4 with 3, domain 8 with
+none), whose records are random points and evaluations: the statement needs no real circuit.  Ten records, two per key, are interleaved so
+that neighbouring lanes of a wave never share a key."""
+import copy
+import random
+
+import numpy as np
+import pytest
+
+from distributed_plonk_amd import _ffi
+from distributed_plonk_amd import fr as _fr
+from distributed_plonk_amd import transcript as TR
+from distributed_plonk_amd import verifier as VF
+from distributed_plonk_amd._ffi import PlonkError
+from distributed_plonk_amd.transcript import PlonkTranscript
+from tests.circuit_cases import _proved, prove_synthetic
+from tests.test_gpu_batch_verify import CURVES, TAU, _ref_ok
+
+pytestmark = pytest.mark.gpu
+
+ERR_ARG, ERR_DOMAIN = -1, -2
+NAMES = ["beta", "gamma", "alpha", "zeta", "v", "u"]
+KEY_NAMES = ["big", "small", "dom1", "dom2", "zero"]
+KEY_INPUTS = [3, 1, 2, 3, 0]
+_SETUP, _REF, _SMALL = {}, {}, {}
+
+
+def _mods(curve):
+    from oracle import bigint_ref as B
+    from oracle import verifier_ref as V
+    return B, V, B.CURVES[curve], _fr.FIELDS[curve]
+
+
+def _mul(curve, s):
+    B, V, cv, _ = _mods(curve)
+    return V.point_limbs(cv, B.scalar_mul(cv, s % cv.fr.p, (cv.gx, cv.gy)))
+
+
+def _proof(curve, pts, evs):
+    f = _fr.FIELDS[curve]
+    e = [f.to_limbs(x) for x in evs]
+    return dict(wires_poly_comms=list(pts[:5]), prod_perm_poly_comm=pts[5], split_quot_poly_comms=list(pts[6:11]), opening_proof=pts[11],
+                shifted_opening_proof=pts[12], wires_evals=e[:5], wire_sigma_evals=e[5:9], perm_next_eval=e[9])
+
+
+def _small_circuit(gpu_workers, oracle, curve, cid):
+    """The smallest instance the prover accepts at or above 2^5 gates, with one public input: (log_n, vk, pub, two proofs)."""
+    if curve not in _SMALL:
+        for log_n in range(5, 11):
+            try:
+                _SMALL[curve] = (log_n,) + prove_synthetic(gpu_workers(curve), oracle, cid, log_n, 2, seed=11, num_inputs=1)
+                break
+            except (ValueError, PlonkError):
+                continue
+    return _SMALL[curve]
+
+
+def _setup(gpu_workers, oracle, curve, cid):
+    """(worker, [5 key dicts], [10 cases]); a case: key (index), pub [m, 4], proof, honest.  Cases 2i and 2i + 1 belong to key i."""
+    if curve not in _SETUP:
+        B, V, cv, f = _mods(curve)
+        r = f.p
+        rng = random.Random(8200 + cid)
+        w, vk_big, pub_big, proofs_big = _proved(gpu_workers, oracle, curve, cid)
+        log_small, vk_small, pub_small, proofs_small = _small_circuit(gpu_workers, oracle, curve, cid)
+        assert vk_big["domain_size"] == 1 << 10 and len(pub_big) == 3
+        assert 5 <= log_small < 10 and vk_small["domain_size"] == 1 << log_small and len(pub_small) == 1
+        R13 = [_mul(curve, rng.randrange(1, r)) for _ in range(13)]
+        S5 = [_mul(curve, rng.randrange(1, r)) for _ in range(5)]
+        stmt = lambda log_n: dict(domain_size=1 << log_n, k=[f.to_limbs(x) for x in [1] + [rng.randrange(2, r) for _ in range(4)]],
+                                  selector_comms=list(R13), sigma_comms=list(S5))
+        keys = [vk_big, vk_small, stmt(1), stmt(2), stmt(3)]
+        keys = [dict(vk, num_inputs=m) for vk, m in zip(keys, KEY_INPUTS)]
+        cases = []
+        for i in range(2):
+            cases.append(dict(key=0, pub=np.asarray(pub_big, dtype=np.uint64), proof=proofs_big[i], honest=True))
+        for i in range(2):
+            cases.append(dict(key=1, pub=np.asarray(pub_small, dtype=np.uint64), proof=proofs_small[i], honest=True))
+        G = _mul(curve, 1)
+        for ki in (2, 3, 4):
+            for pts in ([G] * 13, S5 + R13[:8]):
+                pub = f.vec_to_limbs([rng.randrange(r) for _ in range(KEY_INPUTS[ki])]) if KEY_INPUTS[ki] else np.zeros((0, 4), np.uint64)
+                cases.append(dict(key=ki, pub=pub, proof=_proof(curve, pts, [rng.randrange(r) for _ in range(10)]), honest=False))
+        for n, c in enumerate(cases):
+            c["label"] = f"{KEY_NAMES[c['key']]}{n % 2}"
+            c["rho"] = rng.randrange(2, r)
+        _SETUP[curve] = (keys, cases)
+    return (gpu_workers(curve),) + _SETUP[curve]
+
+
+def _reference(curve, keys, case):
+    """Challenges, the integer statement and rho * (Bp, A) of one case under ITS key; computed once."""
+    k = (curve, case["label"])
+    if k not in _REF:
+        B, V, cv, _ = _mods(curve)
+        vk = keys[case["key"]]
+        ch = V.derive_challenges(PlonkTranscript(curve), vk, list(case["pub"]), case["proof"])
+        s = V.folded_statement(cv, vk, case["pub"], case["proof"], ch)
+        one = [V.point_limbs(cv, s[n])[0] for n in ("Bp", "A")]
+        scaled = [V.point_limbs(cv, B.scalar_mul(cv, case["rho"], s[n]))[0] for n in ("Bp", "A")]
+        _REF[k] = dict(ch=ch, pi_eval=s["pi_eval"], lin_eval=s["lin_eval"], batch_eval=s["batch_eval"], one=one, scaled=scaled)
+    return _REF[k]
+
+
+INTERLEAVED = [0, 2, 4, 6, 8, 1, 3, 5, 7, 9]               # case numbers: keys 0 1 2 3 4 0 1 2 3 4
+
+
+def _rho_limbs(curve, rhos):
+    return np.stack([_fr.FIELDS[curve].to_limbs(x) for x in rhos])
+
+
+@pytest.fixture(scope="module")
+def key_sets(gpu_workers, oracle):
+    made = {}
+
+    def get(curve, cid):
+        if curve not in made:
+            w, keys, _ = _setup(gpu_workers, oracle, curve, cid)
+            made[curve] = VF.VerifyKeySet(w, keys)
+        return made[curve]
+
+    yield get
+    for ks in made.values():
+        ks.close()
+
+
+# ------------------------------------------------------------------------------------------------ parity with the reference
+@pytest.mark.parametrize("K", [1, 2, 3, 64, 65])
+@pytest.mark.parametrize("curve,cid", CURVES)
+def test_mixed_batch_matches_the_reference(gpu_workers, oracle, key_sets, curve, cid, K):
+    B, V, cv, f = _mods(curve)
+    w, keys, cases = _setup(gpu_workers, oracle, curve, cid)
+    ks = key_sets(curve, cid)
+    order = [INTERLEAVED[(j + K) % 10] for j in range(K)]
+    if K == 64:
+        random.Random(64).shuffle(order)                   # a shuffled batch; the others alternate keys strictly
+    else:
+        assert all(cases[a]["key"] != cases[b]["key"] for a, b in zip(order, order[1:]))
+    if K >= 64:
+        assert {cases[n]["key"] for n in order} == set(range(5))
+    batch = [cases[n] for n in order]
+    idx = [c["key"] for c in batch]
+    pubs, prfs = [c["pub"] for c in batch], [c["proof"] for c in batch]
+    pts1, st1, dbg = VF.device_verify_multi(w, ks, idx, pubs, prfs, _rho_limbs(curve, [1] * K), debug=True)
+    pts_r, st_r, _ = VF.device_verify_multi(w, ks, idx, pubs, prfs, _rho_limbs(curve, [c["rho"] for c in batch]))
+    assert not st1.any() and not st_r.any()
+    for j, c in enumerate(batch):
+        at = (j, c["label"])
+        ref = _reference(curve, keys, c)
+        for i, name in enumerate(NAMES):
+            assert np.array_equal(dbg[j, i], ref["ch"][name]), (at, name)
+        for i, name in enumerate(["pi_eval", "lin_eval", "batch_eval"]):
+            assert V.fr_int(cv, dbg[j, 6 + i]) == ref[name], (at, name)
+        for which in (0, 1):
+            assert np.array_equal(pts1[j, which], ref["one"][which]), (at, "rho = 1", which)
+            assert np.array_equal(pts_r[j, which], ref["scaled"][which]), (at, "rho", which)
+
+
+# ------------------------------------------------------------------------------------------------ one key: the old entry point, bit for bit
+def _off_curve(pt):
+    xy = np.array(pt[0], dtype=np.uint64).copy()
+    xy[0] ^= np.uint64(1)
+    return xy, False
+
+
+@pytest.mark.parametrize("curve,cid", CURVES)
+def test_one_key_equals_the_single_key_entry_point(gpu_workers, oracle, curve, cid):
+    w, keys, cases = _setup(gpu_workers, oracle, curve, cid)
+    f = _fr.FIELDS[curve]
+    vk, pub = keys[0], cases[0]["pub"]
+    bad_point = dict(cases[1]["proof"], opening_proof=_off_curve(cases[1]["proof"]["opening_proof"]))
+    bad_eval = dict(cases[0]["proof"], perm_next_eval=f.to_limbs((f.from_limbs(cases[0]["proof"]["perm_next_eval"]) + 1) % f.p))
+    prfs = [cases[0]["proof"], bad_point, cases[1]["proof"], bad_eval, cases[0]["proof"]]
+    K = len(prfs)
+    rho = VF._rhos(curve, K, 77)
+    pts_old, st_old, _ = VF.device_verify(w, vk, [pub] * K, prfs, rho)
+    with VF.VerifyKeySet(w, [vk]) as ks:
+        assert ks.n_vks == 1
+        pts_new, st_new, _ = VF.device_verify_multi(w, ks, [0] * K, [pub] * K, prfs, rho)
+        assert [int(s) for s in st_old] == [0, 1, 0, 0, 0]
+        assert np.array_equal(st_new, st_old) and np.array_equal(pts_new, pts_old)
+        key = VF.OpenKey.from_trapdoor(curve, TAU)
+        st, st_m = {}, {}
+        want = VF.batch_verify(w, vk, key, [pub] * K, prfs, stats=st, _rho=rho)
+        assert want == [True, False, True, False, True]
+        assert VF.batch_verify_multi(w, ks, key, [0] * K, [pub] * K, prfs, stats=st_m, _rho=rho) == want
+        assert st_m["status"] == st["status"]
+
+
+# ------------------------------------------------------------------------------------------------ verdicts
+@pytest.mark.parametrize("curve,cid", CURVES)
+def test_honest_proofs_of_both_circuits_in_one_pairing(gpu_workers, oracle, key_sets, curve, cid):
+    w, keys, cases = _setup(gpu_workers, oracle, curve, cid)
+    batch = [cases[0], cases[2], cases[1], cases[3]]
+    for c in batch:
+        assert _ref_ok(curve, keys[c["key"]], c["pub"], c["proof"])
+    st = {}
+    key = VF.OpenKey.from_trapdoor(curve, TAU)
+    args = ([c["key"] for c in batch], [c["pub"] for c in batch], [c["proof"] for c in batch])
+    assert VF.batch_verify_multi(w, key_sets(curve, cid), key, *args, seed=1, stats=st) == [True] * 4
+    assert st["pairing_checks"] == 1 and st["status"] == [0] * 4
+    # the same from a plain list of key dicts, wrapped and closed inside; keys without a count take it from their first proof
+    plain = [{k: v for k, v in vk.items() if k != "num_inputs"} for vk in keys[:2]]
+    assert VF.batch_verify_multi(w, plain, key, *args, seed=1, stats=st) == [True] * 4 and st["pairing_checks"] == 1
+    assert VF.batch_verify_multi(w, plain, key, [], [], []) == []
+
+
+@pytest.mark.parametrize("what", ["other_circuit", "other_key", "public_input", "evaluation"])
+@pytest.mark.parametrize("curve,cid", CURVES)
+def test_a_wrong_proof_is_rejected_alone(gpu_workers, oracle, key_sets, curve, cid, what):
+    w, keys, cases = _setup(gpu_workers, oracle, curve, cid)
+    f = _fr.FIELDS[curve]
+    good = cases[2]                                        # an honest proof of the small circuit beside the wrong one
+    c = cases[0]
+    idx, pub, proof = c["key"], c["pub"], c["proof"]
+    if what == "other_circuit":                            # the small circuit's index: its key wants one public input, a verdict of the span check
+        idx = 1
+    elif what == "other_key":                              # an honest proof of the 2^10 circuit under the 3-input statement key dom2
+        idx = 3
+        assert KEY_INPUTS[idx] == pub.shape[0]
+    elif what == "public_input":
+        pub = pub.copy()
+        pub[1] = f.to_limbs((f.from_limbs(pub[1]) + 1) % f.p)
+    else:
+        proof = dict(proof, wires_evals=[f.to_limbs((f.from_limbs(x) + (i == 2)) % f.p) for i, x in enumerate(proof["wires_evals"])])
+    assert not _ref_ok(curve, keys[idx], pub, proof)        # the reference under the same (wrong) key rejects too
+    st = {}
+    got = VF.batch_verify_multi(w, key_sets(curve, cid), VF.OpenKey.from_trapdoor(curve, TAU), [idx, good["key"]], [pub, good["pub"]],
+                                [proof, good["proof"]], seed=4, stats=st)
+    assert got == [False, True]
+    if what == "other_circuit":
+        assert st["status"] == [64, 0] and st["pairing_checks"] == 1
+    else:                                                  # the root, the wrong leaf, and its neighbour
+        assert st["status"] == [0, 0] and st["pairing_checks"] == 3
+
+
+@pytest.mark.parametrize("curve,cid", CURVES)
+def test_bad_index_and_bad_span_are_verdicts_that_read_nothing(gpu_workers, oracle, key_sets, curve, cid):
+    B, V, cv, f = _mods(curve)
+    w, keys, cases = _setup(gpu_workers, oracle, curve, cid)
+    ks = key_sets(curve, cid)
+    FAR = 1 << 40                                          # in Fr elements: 32 TiB beyond a buffer that holds exactly pub_total of them
+    # lane: 0 ok | 1 overruns pub_total | 2 starts beyond its end (decreasing) | 3 ok | 4 index n_vks | 5 ok | 6 two inputs for a key of 3 | 7 ok
+    lanes = [cases[0], cases[2], cases[1], cases[3], cases[0], cases[6], cases[1], cases[8]]
+    idx = [c["key"] for c in lanes]
+    idx[4] = ks.n_vks
+    pubs = [c["pub"] for c in lanes]
+    pubs[1] = pubs[2] = np.zeros((0, 4), np.uint64)        # their inputs are not in the buffer at all
+    pubs[6] = pubs[6][:2]
+    off = [0, 3, FAR, 3, 4, 7, 10, 12, 12]
+    assert [int(x) for x in np.concatenate([[0], np.cumsum([p.shape[0] for p in pubs])])] == [0, 3, 3, 3, 4, 7, 10, 12, 12]
+    expect = [0, 64, 64, 0, 32, 0, 64, 0]
+    K = len(lanes)
+    pts, status, dbg = VF.device_verify_multi(w, ks, idx, pubs, [c["proof"] for c in lanes], _rho_limbs(curve, [1] * K), debug=True, _offsets=off)
+    assert [int(s) for s in status] == expect
+    for j, c in enumerate(lanes):
+        if expect[j]:
+            assert not pts[j].any() and not dbg[j].any(), j
+        else:
+            ref = _reference(curve, keys, c)
+            assert np.array_equal(pts[j, 0], ref["one"][0]) and np.array_equal(pts[j, 1], ref["one"][1]), j
+    # both bits at once: an index out of range on a span that overruns
+    idx2 = list(idx)
+    idx2[1] = 0xFFFFFFFF
+    _, status, _ = VF.device_verify_multi(w, ks, idx2, pubs, [c["proof"] for c in lanes], _rho_limbs(curve, [1] * K), _offsets=off)
+    assert [int(s) for s in status] == [0, 32 | 64, 64, 0, 32, 0, 64, 0]
+    # no public input anywhere: d_pub_inputs is NULL
+    zero = [cases[8], cases[9], cases[8]]
+    pts, status, _ = VF.device_verify_multi(w, ks, [4, 4, 5], [c["pub"] for c in zero], [c["proof"] for c in zero], _rho_limbs(curve, [1] * 3))
+    assert [int(s) for s in status] == [0, 0, 32] and np.array_equal(pts[1, 1], _reference(curve, keys, cases[9])["one"][1]) and not pts[2].any()
+    # the verdicts: rejected without a pairing of their own, the honest neighbours accepted
+    st = {}
+    batch = [cases[0], cases[2], cases[1], cases[3]]
+    pubs = [c["pub"] for c in batch]
+    pubs[3] = np.concatenate([pubs[3], pubs[3]])           # two inputs for a key of one
+    got = VF.batch_verify_multi(w, ks, VF.OpenKey.from_trapdoor(curve, TAU), [0, ks.n_vks, 0, 1], pubs, [c["proof"] for c in batch], seed=6, stats=st)
+    assert got == [True, False, True, False] and st["status"] == [0, 32, 0, 64] and st["pairing_checks"] == 1
+
+
+# ------------------------------------------------------------------------------------------------ bisection over the device tree
+@pytest.mark.parametrize("curve,cid", CURVES)
+def test_bisection_finds_the_bad_proofs(gpu_workers, oracle, key_sets, curve, cid):
+    w, keys, cases = _setup(gpu_workers, oracle, curve, cid)
+    f = _fr.FIELDS[curve]
+    key = VF.OpenKey.from_trapdoor(curve, TAU)
+    K = 64
+    batch = [cases[(0, 2, 1, 3)[i % 4]] for i in range(K)]
+    idx, pubs, prfs = [c["key"] for c in batch], [c["pub"] for c in batch], [c["proof"] for c in batch]
+    bad_idx = [3, 31, 50]
+    ref = {}                                               # the per-proof reference, once per distinct (key, proof)
+    for i in bad_idx:
+        b = copy.deepcopy(prfs[i])
+        b["perm_next_eval"] = f.to_limbs((f.from_limbs(b["perm_next_eval"]) + i) % f.p)
+        prfs[i] = b
+    want = []
+    for i in range(K):
+        if (idx[i], id(prfs[i])) not in ref:
+            ref[(idx[i], id(prfs[i]))] = _ref_ok(curve, keys[idx[i]], pubs[i], prfs[i])
+        want.append(ref[(idx[i], id(prfs[i]))])
+    assert [i for i, v in enumerate(want) if not v] == bad_idx and len(ref) == 7
+    st = {}
+    got = VF.batch_verify_multi(w, key_sets(curve, cid), key, idx, pubs, prfs, seed=2, stats=st)
+    assert got == want
+    assert st["pairing_checks"] <= 1 + 2 * len(bad_idx) * 6
+    assert VF.batch_verify_multi(w, key_sets(curve, cid), key, idx, pubs, prfs, seed=2) == got
+
+
+# ------------------------------------------------------------------------------------------------ the sum tree on raw points
+def _tree_case(curve, k, masked):
+    """k pairs over a pool of small multiples of G with the exceptional sibling pairs in front, and the integer tree of their sums."""
+    B, V, cv, _ = _mods(curve)
+    rng = random.Random(1000 + k)
+    G = (cv.gx, cv.gy)
+    pool = [B.scalar_mul(cv, s, G) for s in (1, 2, 3, 5, 7, 11, cv.fr.p - 1, cv.fr.p - 2)] + [B.INF]
+    P, Q = pool[3], pool[4]
+    leaves = [[rng.choice(pool), rng.choice(pool)] for _ in range(k)]
+    front = [[P, Q], [P, B.affine_neg(cv, Q)],            # slot 0: P + P (doubling), slot 1: Q + (-Q) (infinity)
+             [B.INF, B.INF], [P, B.INF],                   # slot 0: O + P, slot 1: O + O
+             [B.affine_neg(cv, P), Q]]                     # node (0, 1) + node (2, 3) in slot 1 is O + O again
+    for j in range(min(k, len(front))):
+        leaves[j] = front[j]
+    Pw = VF.tree_leaves(k)
+    tree = [None] * (2 * Pw - 1)
+    for j in range(Pw):
+        tree[Pw - 1 + j] = list(leaves[j]) if j < k and j not in masked else [B.INF, B.INF]
+    for i in range(Pw - 2, -1, -1):
+        tree[i] = [B.affine_add(cv, tree[2 * i + 1][s], tree[2 * i + 2][s]) for s in (0, 1)]
+    to_limbs = lambda pair: np.stack([V.point_limbs(cv, p)[0] for p in pair])
+    return np.stack([to_limbs(p) for p in leaves]), np.stack([to_limbs(p) for p in tree])
+
+
+@pytest.mark.parametrize("k", [1, 2, 3, 5, 64, 65, 129])
+@pytest.mark.parametrize("curve,cid", CURVES)
+def test_sum_tree_equals_the_integer_sums(gpu_workers, curve, cid, k):
+    w = gpu_workers(curve)
+    n64 = VF._q64(curve)
+    for masked in [set()] + ([{1}, {0, k - 1}] if k >= 2 else [{0}]):      # {1}: takes -Q away from the pair that cancels
+        points, want = _tree_case(curve, k, masked)
+        nodes = 2 * VF.tree_leaves(k) - 1
+        assert want.shape == (nodes, 2, 2 * n64)
+        mask = None
+        if masked:
+            mask = np.zeros(k, np.uint32)
+            mask[sorted(masked)] = [1, 0x80000000][:len(masked)]
+        bufs = [w.alloc(points.nbytes).upload(points), w.alloc(want.nbytes)] + ([w.alloc(k * 4).upload(mask)] if masked else [])
+        try:
+            w.memset_dev(bufs[1].ptr, 0xFF, want.nbytes)    # every node, padding leaves included, has to be written
+            w.g1_sum_tree_dev(bufs[0].ptr, k, bufs[2].ptr if masked else 0, bufs[1].ptr)
+            got = bufs[1].download(want.shape)
+        finally:
+            for b in bufs:
+                b.free()
+        bad = [i for i in range(nodes) if not np.array_equal(got[i], want[i])]
+        assert not bad, (k, sorted(masked), bad[:8])
+        assert np.array_equal(VF.g1_sum_tree(w, points, mask), want)
+        if k == 2:                                          # the reference's own P + P and Q + (-Q); without -Q the root is Q
+            assert want[0].any() == (len(masked) < 2) and want[0, 1].any() == (masked == {1})
+
+
+@pytest.mark.parametrize("curve,cid", CURVES)
+def test_sum_tree_of_nothing_writes_nothing(gpu_workers, curve, cid):
+    w = gpu_workers(curve)
+    d = w.alloc(256)
+    try:
+        w.memset_dev(d.ptr, 0xA5, 256)
+        w.g1_sum_tree_dev(d.ptr, 0, 0, d.ptr)
+        w.g1_sum_tree_dev(0, 0, 0, 0)
+        assert (d.download((256,), dtype=np.uint8) == 0xA5).all()
+        for args in ((0, 1, 0, d.ptr), (d.ptr, 1, 0, 0), (d.ptr, (1 << 22) + 1, 0, d.ptr)):
+            with pytest.raises(PlonkError):
+                w.g1_sum_tree_dev(*args)
+    finally:
+        d.free()
+    assert VF.g1_sum_tree(w, np.zeros((0, 2, 2 * VF._q64(curve)), np.uint64)).shape[0] == 0
+
+
+# ------------------------------------------------------------------------------------------------ from bytes
+@pytest.mark.parametrize("curve,cid", CURVES)
+def test_batch_verify_multi_bytes(gpu_workers, oracle, key_sets, curve, cid):
+    from tests import codec_ref as R
+    from tests.test_gpu_codec import no_point_x, point_at
+    w, keys, cases = _setup(gpu_workers, oracle, curve, cid)
+    ks = key_sets(curve, cid)
+    key = VF.OpenKey.from_trapdoor(curve, TAU)
+    batch = [cases[0], cases[2], cases[1], cases[3]]
+    idx = [c["key"] for c in batch]
+    blobs = [TR.serialize_proof(curve, c["proof"]) for c in batch]
+    pubs = [b"".join(TR.serialize_fr(curve, x) for x in c["pub"]) for c in batch]
+    assert [len(p) for p in pubs] == [96, 32, 96, 32]
+    st = {}
+    assert VF.batch_verify_multi_bytes(w, ks, key, idx, pubs, blobs, seed=1, stats=st) == [True] * 4
+    assert st["pairing_checks"] == 1 and st["decode_status"] == [0] * 4 and st["status"] == [0] * 4
+    at = point_at(curve, 8)
+    no_point = blobs[1][:at] + no_point_x(curve) + blobs[1][at + R.NBYTES[curve]:]
+    assert VF.batch_verify_multi_bytes(w, ks, key, idx, pubs, [blobs[0], no_point, blobs[2], blobs[3]], seed=2, stats=st) == [True, False, True, True]
+    assert st["decode_status"] == [0, 1, 0, 0] and st["pairing_checks"] == 1
+    # a public input that is no canonical scalar rejects its proof alone; so does a blob that is short by one element (status 64)
+    r_bytes = R.fr_modulus(curve).to_bytes(32, "little")
+    assert VF.batch_verify_multi_bytes(w, ks, key, idx, [pubs[0], pubs[1], r_bytes + pubs[2][32:], pubs[3]], blobs, seed=3, stats=st) \
+        == [True, True, False, True]
+    assert st["decode_status"] == [0, 0, 8, 0] and st["pairing_checks"] == 1
+    assert VF.batch_verify_multi_bytes(w, ks, key, idx, [pubs[0][:64]] + pubs[1:], blobs, seed=3, stats=st) == [False, True, True, True]
+    assert st["status"] == [64, 0, 0, 0] and st["decode_status"] == [0] * 4
+    assert VF.batch_verify_multi_bytes(w, ks, key, [], [], []) == []
+    with pytest.raises(ValueError):
+        VF.batch_verify_multi_bytes(w, ks, key, idx, [pubs[0][:95]] + pubs[1:], blobs)
+    with pytest.raises(ValueError):
+        VF.batch_verify_multi_bytes(w, ks, key, idx, pubs[:3], blobs)
+
+
+# ------------------------------------------------------------------------------------------------ argument errors
+@pytest.mark.parametrize("curve,cid", CURVES)
+def test_argument_errors_name_the_key(gpu_workers, oracle, key_sets, curve, cid):
+    w, keys, cases = _setup(gpu_workers, oracle, curve, cid)
+    ks = key_sets(curve, cid)
+    lib = _ffi.lib()
+    d = w.alloc(8192)                                      # one zeroed record, then index, offsets, rho, output pair and status apart from each other
+    at = lambda nbytes: d.ptr + nbytes
+
+    def call(vks, n_vks, k=1, idx=True):
+        return lib.plonk_verify_batch_multi_dev(w.ctx, vks, n_vks, k, at(0), at(2048) if idx else None, None, at(2304), 0, at(2560), at(3072), at(4096), None)
+
+    def error():
+        return lib.plonk_last_error().decode()
+
+    try:
+        w.memset_dev(d.ptr, 0, 8192)
+        assert call(ks.keys, 0) == ERR_ARG and call(ks.keys, 4097) == ERR_ARG
+        assert call(None, 1) == ERR_ARG
+        assert call(ks.keys, ks.n_vks, idx=False) == ERR_ARG
+        bad = (_ffi.VerifyKey * ks.n_vks)(*ks.keys)
+        bad[3].domain_size = 1000
+        assert call(bad, ks.n_vks) == ERR_DOMAIN and "key 3" in error()
+        assert call(bad, 3) == 0                # the first three alone are sound (k = 1 all-zero record under key 0: a verdict)
+        bad = (_ffi.VerifyKey * ks.n_vks)(*ks.keys)
+        bad[2].d_comms = None
+        assert call(bad, ks.n_vks) == ERR_ARG and "key 2" in error()
+        assert call(bad, ks.n_vks, k=0) == ERR_ARG and "key 2" in error()      # keys are checked before the batch size
+        assert call(ks.keys, ks.n_vks, k=0) == 0
+        w.sync()
+        with pytest.raises(PlonkError):
+            _ffi.check(call(ks.keys, ks.n_vks, k=(1 << 22) + 1))
+    finally:
+        d.free()
+    # the Python surface: a key of the wrong shape, a key of the other curve, counts that do not match the keys
+    with pytest.raises(ValueError, match="verifying key shape"):
+        VF.VerifyKeySet(w, [dict(keys[0], sigma_comms=keys[0]["sigma_comms"][:4])])
+    other = "bls12_381" if curve == "bn254" else "bn254"
+    foreign = (np.zeros(2 * VF._q64(other), np.uint64), True)
+    with pytest.raises(ValueError, match="not on"):
+        VF.VerifyKeySet(w, [dict(keys[2], selector_comms=[foreign] * 13, sigma_comms=[foreign] * 5)])
+    with pytest.raises(ValueError):
+        VF.VerifyKeySet(w, [])
+    with pytest.raises(ValueError):
+        VF.VerifyKeySet(w, keys, num_inputs=[1, 2])
+    with pytest.raises(ValueError):
+        VF.VerifyKeySet(w, [{k: v for k, v in keys[0].items() if k != "num_inputs"}])
+    with pytest.raises(ValueError):
+        VF.batch_verify_multi(w, ks, VF.OpenKey.from_trapdoor(curve, TAU), [0], [cases[0]["pub"]] * 2, [cases[0]["proof"]] * 2)
