@@ -5,12 +5,15 @@ the ~30 scalars of the linearised check and the two multi-scalar sums rho_k * A_
 
     A = W_zeta + u W_zeta_omega,   B = zeta W_zeta + u zeta w W_zeta_omega + F + u [z] - (E + u z(zeta w)) G.
 
-The host adds the K pairs and runs ONE two-pairing check e(sum rho A, beta H) * e(-sum rho B, H) == 1 (`plonk_pairing_check`); a failed
-batch is bisected, so f bad proofs cost O(f log K) pairing checks.  rho_k are drawn from `secrets` unless a seed is given (tests).
+The device folds the K pairs into a sum tree (`plonk_g1_sum_tree_dev`); the host reads the root back and runs ONE two-pairing check
+e(sum rho A, beta H) * e(-sum rho B, H) == 1 (`plonk_pairing_check`).  A failed batch is bisected over tree nodes read back one at a time
+(`bisect_tree`), with no point addition on the host, so f bad proofs cost O(f log K) pairing checks.  rho_k are drawn from `secrets`
+unless a seed is given (tests).
 
-`batch_verify_multi` / `batch_verify_multi_bytes` take a verifying key PER PROOF (`VerifyKeySet`, `plonk_verify_batch_multi_dev`) and fold
-the batch on the device into a sum tree (`plonk_g1_sum_tree_dev`): the host pairs the root and bisects over tree nodes it reads back
-(`bisect_tree`), with no point addition of its own.  The one-key functions keep the host fold.
+`batch_verify_multi` / `batch_verify_multi_bytes` take a verifying key PER PROOF (`VerifyKeySet`, `plonk_verify_batch_multi_dev`); the
+`_bytes` functions take serialized proofs and public inputs and decode them on the device.  All four batch functions are one sequence of
+stages — the batch on the device, the per-proof pairs, the fold (`_fold`) — and differ in where the records come from and in which of the
+two per-proof entry points they launch.
 
 The transcript labels of the two opening proofs and of u (b"open_proof", b"shifted_open_proof", b"u") are those of jf-plonk's verifier as
 far as the public sources show; like the serialised `Proof` layout they are not pinned by a reference-generated proof.
@@ -140,21 +143,27 @@ class OpenKey:
         return cls(curve, xy, pts[0], pts[1])
 
 
-def _jac(curve: str, xy: np.ndarray) -> np.ndarray:
-    n = _q64(curve)
-    one = np.array(_fq_mont(curve, 1), dtype=np.uint64)
-    if not xy.any():
-        return np.concatenate([one, one, np.zeros(n, np.uint64)])
-    return np.concatenate([xy, one])
+class _Buffers(list):
+    """The device buffers of one call: `with _Buffers(worker) as bufs` frees every one of them on every exit, exceptions included."""
 
+    def __init__(self, worker):
+        super().__init__()
+        self.worker = worker
 
-def _sum_points(worker, curve: str, pts: Sequence[np.ndarray]) -> np.ndarray:
-    acc = _jac(curve, np.zeros(2 * _q64(curve), np.uint64))
-    for p in pts:
-        if p.any():
-            acc = worker.g1_add(acc, _jac(curve, p))
-    xy, inf = worker.g1_to_affine(acc)
-    return np.zeros_like(xy) if inf else xy
+    def alloc(self, nbytes: int):
+        self.append(self.worker.alloc(max(nbytes, 8)))
+        return self[-1]
+
+    def upload(self, arr: np.ndarray) -> int:
+        """The array in a buffer of its own: the device pointer, 0 for an empty array (nothing is allocated for one)."""
+        return self.alloc(arr.nbytes).upload(arr).ptr if arr.nbytes else 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for b in self:
+            b.free()
 
 
 def _vk_state(curve: str, vk: dict, num_inputs: int) -> _ffi.VerifyKey:
@@ -185,158 +194,100 @@ def proof_record(curve: str, proof: dict) -> np.ndarray:
 
 def device_verify(worker, vk: dict, public_inputs_list, proofs, rho: np.ndarray, debug: bool = False):
     """The device part for K proofs: (points [K, 2 (rho B, rho A), 2Q] u64, status [K] u32, debug [K, 9, 4] or None)."""
-    curve = worker.curve_name
-    n64 = _q64(curve)
     K = len(proofs)
+    pis, num_inputs = _one_key_inputs(K, public_inputs_list, rho)
+    with _Buffers(worker) as bufs:
+        d_recs, d_pub = _upload_batch(bufs, proofs, pis)
+        return device_verify_records(worker, vk, num_inputs, K, d_recs, d_pub, rho, debug)
+
+
+def device_verify_records(worker, vk: dict, num_inputs: int, K: int, d_recs: int, d_pub: int, rho: np.ndarray, debug: bool = False):
+    """What device_verify does after the upload: K proof records and K x num_inputs public inputs already on the device (pointers) ->
+    (points, status, debug) as device_verify returns them."""
+    with _Buffers(worker) as bufs:
+        return _download_pairs(K, *_launch_pairs(bufs, K, rho, debug, _one_key_launch(bufs, vk, num_inputs, K, d_recs, d_pub)))
+
+
+# ------------------------------------------------------------------------------------------------ the stages every entry point shares
+def _one_key_inputs(K: int, public_inputs_list, rho: np.ndarray):
+    """(public inputs as [m, 4] arrays, m): the one-key entry point wants the same count m under every proof."""
     if len(public_inputs_list) != K or rho.shape[0] != K:
         raise ValueError("one public-input list and one rho per proof")
     pis = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 4) for p in public_inputs_list]
     num_inputs = pis[0].shape[0] if K else 0
     if any(p.shape[0] != num_inputs for p in pis):
         raise ValueError("every proof of a batch needs the same number of public inputs")
-    recs = np.stack([proof_record(curve, p) for p in proofs]) if K else np.zeros((0, 2 * n64 * NPTS + 4 * NEVALS), np.uint64)
-    pub = np.concatenate(pis) if num_inputs else np.zeros((1, 4), np.uint64)
-    bufs = []
-    try:
-        for arr in (recs, pub):
-            bufs.append(worker.alloc(max(arr.nbytes, 8)))
-            bufs[-1].upload(arr)
-        return device_verify_records(worker, vk, num_inputs, K, bufs[0].ptr, bufs[1].ptr, rho, debug)
-    finally:
-        for b in bufs:
-            b.free()
+    return pis, num_inputs
 
 
-def device_verify_records(worker, vk: dict, num_inputs: int, K: int, d_recs: int, d_pub: int, rho: np.ndarray, debug: bool = False):
-    """What device_verify does after the upload: K proof records and K x num_inputs public inputs already on the device (pointers) ->
-    (points, status, debug) as device_verify returns them."""
-    curve = worker.curve_name
-    n64 = _q64(curve)
+def _upload_batch(bufs: _Buffers, proofs, pis, *more):
+    """A batch of proof dicts on the device: the pointers of the records, of the concatenated public inputs and of every array of `more`
+    (key indices, offsets), 0 for an empty array."""
+    curve = bufs.worker.curve_name
+    recs = np.stack([proof_record(curve, p) for p in proofs]) if len(proofs) else np.zeros((0, 2 * _q64(curve) * NPTS + 4 * NEVALS), np.uint64)
+    return [bufs.upload(arr) for arr in (recs, np.concatenate(pis + [np.zeros((0, 4), np.uint64)]), *more)]
+
+
+def _decode_batch(bufs: _Buffers, public_inputs_bytes: Sequence[bytes], proof_blobs):
+    """A batch as provers send it, decoded on the device: the proofs by codec.proofs_from_bytes_dev, all public inputs (32 bytes each, any
+    number per proof) by ONE plonk_fr_from_bytes_dev launch over their concatenation.  (d_recs, d_pub or 0, the K + 1 offsets of the proofs'
+    spans in d_pub, decode [K] u32): decode[j] ORs the codec's status words of proof j and of its inputs."""
+    from . import codec
+    worker, K = bufs.worker, len(proof_blobs)
+    d_recs, decode = codec.proofs_from_bytes_dev(worker, proof_blobs)
+    bufs.append(d_recs)
+    off = np.concatenate([[0], np.cumsum([len(p) // 32 for p in public_inputs_bytes])]).astype(np.uint64)
+    total = int(off[-1])
+    d_pub = 0
+    if total:
+        d_raw = bufs.upload(np.frombuffer(b"".join(public_inputs_bytes), dtype=np.uint8))
+        d_pub = bufs.alloc(total * 32).ptr
+        d_st = bufs.alloc(total * 4)
+        worker.memset_dev(d_st.ptr, 0, total * 4)
+        worker.fr_from_bytes_dev(d_raw, 32, total, d_pub, 4, d_st.ptr, 1)
+        st = d_st.download((total,), dtype=np.uint32)
+        decode = decode | np.array([np.bitwise_or.reduce(st[int(off[j]):int(off[j + 1])], initial=0) for j in range(K)], dtype=np.uint32)
+    return d_recs.ptr, d_pub, off, np.ascontiguousarray(decode, dtype=np.uint32)
+
+
+def _one_key_launch(bufs: _Buffers, vk: dict, num_inputs: int, K: int, d_recs: int, d_pub: int):
+    """The launch of `plonk_verify_batch_dev` under vk for _launch_pairs, the key's 18 commitments uploaded.  A key of the wrong shape raises."""
+    curve = bufs.worker.curve_name
     if len(vk["selector_comms"]) != 13 or len(vk["sigma_comms"]) != 5:
         raise ValueError("verifying key shape")
     key = _vk_state(curve, vk, num_inputs)
-    comms = np.concatenate([_point_xy(curve, c) for c in list(vk["selector_comms"]) + list(vk["sigma_comms"])])
-    bufs = []
-    alloc = lambda nbytes: bufs.append(worker.alloc(max(nbytes, 8))) or bufs[-1]
-    try:
-        d_comms = alloc(comms.nbytes).upload(comms)
-        d_rho = alloc(rho.nbytes).upload(np.ascontiguousarray(rho, dtype=np.uint64))
-        d_out = alloc(K * 2 * 2 * n64 * 8)
-        d_status = alloc(K * 4)
-        d_dbg = alloc(K * 9 * 32) if debug else None
-        if debug:
-            worker.memset_dev(d_dbg.ptr, 0, K * 9 * 32)
-        key.d_comms = d_comms.ptr
-        _ffi.check(_lib().plonk_verify_batch_dev(worker.ctx, C.byref(key), K, d_recs, d_pub if num_inputs else None, d_rho.ptr, d_out.ptr,
-                                                 d_status.ptr, d_dbg.ptr if debug else None))
-        pts = d_out.download((K, 2, 2 * n64))
-        status = d_status.download((K,), dtype=np.uint32)
-        dbg = d_dbg.download((K, 9, 4)) if debug else None
-    finally:
-        for b in bufs:
-            b.free()
-    return pts, status, dbg
+    key.d_comms = bufs.upload(np.concatenate([_point_xy(curve, c) for c in list(vk["selector_comms"]) + list(vk["sigma_comms"])]))
+    return lambda *outputs: bufs.worker.verify_batch_dev(key, K, d_recs, d_pub if num_inputs else 0, *outputs)
+
+
+def _multi_launch(worker, keys: "VerifyKeySet", K: int, d_recs: int, d_idx: int, d_pub: int, d_off: int, pub_total: int):
+    """The launch of `plonk_verify_batch_multi_dev` for _launch_pairs: proof j under keys[idx[j]] on its span of the public inputs."""
+    return lambda *outputs: worker.verify_batch_multi_dev(keys.keys, keys.n_vks, K, d_recs, d_idx, d_pub if pub_total else 0, d_off, pub_total, *outputs)
+
+
+def _launch_pairs(bufs: _Buffers, K: int, rho: np.ndarray, debug: bool, launch):
+    """The per-proof kernels, enqueued: rho uploaded, the buffers of the K output pairs [rho B, rho A], the K status words and (debug) the
+    K x 9 intermediate scalars allocated, and launch(d_rho, d_out, d_status, d_debug or 0) called on their pointers.  (d_out, d_status,
+    d_debug or None): DeviceBuffers that bufs owns."""
+    d_rho = bufs.upload(np.ascontiguousarray(rho, dtype=np.uint64))
+    d_out = bufs.alloc(K * 2 * 2 * _q64(bufs.worker.curve_name) * 8)
+    d_status = bufs.alloc(K * 4)
+    d_dbg = bufs.alloc(K * 9 * 32) if debug else None
+    if debug:
+        bufs.worker.memset_dev(d_dbg.ptr, 0, K * 9 * 32)
+    launch(d_rho, d_out.ptr, d_status.ptr, d_dbg.ptr if debug else 0)
+    return d_out, d_status, d_dbg
+
+
+def _download_pairs(K: int, d_out, d_status, d_dbg):
+    """(points [K, 2, 2Q] u64, status [K] u32, debug [K, 9, 4] or None) as the device_verify functions return them."""
+    return d_out.download((K, 2, d_out.worker.q64 * 2)), d_status.download((K,), dtype=np.uint32), d_dbg.download((K, 9, 4)) if d_dbg else None
 
 
 def _rhos(curve: str, K: int, seed: Optional[int]) -> np.ndarray:
     f = _fr.FIELDS[curve]
     draw = (lambda: secrets.randbelow(f.p - 1) + 1) if seed is None else (lambda r=random.Random(seed): r.randrange(1, f.p))
     return np.stack([f.to_limbs(draw()) for _ in range(K)]) if K else np.zeros((0, 4), np.uint64)
-
-
-def batch_verify(worker, vk: dict, open_key: OpenKey, public_inputs_list, proofs, seed: Optional[int] = None, stats: Optional[dict] = None,
-                 _rho: Optional[np.ndarray] = None) -> list:
-    """One verdict per proof.  `stats` (a dict, optional) receives "pairing_checks" and the status word of every proof ("status")."""
-    curve = worker.curve_name
-    if open_key.curve != curve:
-        raise ValueError("open key and worker are on different curves")
-    K = len(proofs)
-    rho = _rhos(curve, K, seed) if _rho is None else _rho
-    pts, status, _ = device_verify(worker, vk, public_inputs_list, proofs, rho)
-    verdict, checks = _bisect(worker, open_key, pts, [i for i in range(K) if status[i] == 0])
-    if stats is not None:
-        stats["pairing_checks"] = checks
-        stats["status"] = [int(s) for s in status]
-    return verdict
-
-
-def _bisect(worker, open_key: OpenKey, pts: np.ndarray, eligible: list):
-    """(verdicts, pairing checks): one folded pairing check over the eligible proofs, halved while it fails."""
-    curve = worker.curve_name
-    verdict = [False] * pts.shape[0]
-    checks = [0]
-
-    def holds(idx):
-        checks[0] += 1
-        b = _sum_points(worker, curve, [pts[i, 0] for i in idx])
-        a = _sum_points(worker, curve, [pts[i, 1] for i in idx])
-        return pairing_check(curve, [a, _g1_neg(curve, b)], [open_key.beta_h, open_key.h])
-
-    def bisect(idx):
-        if not idx:
-            return
-        if holds(idx):
-            for i in idx:
-                verdict[i] = True
-        elif len(idx) > 1:
-            bisect(idx[:len(idx) // 2])
-            bisect(idx[len(idx) // 2:])
-
-    bisect(list(eligible))
-    return verdict, checks[0]
-
-
-def batch_verify_bytes(worker, vk: dict, open_key: OpenKey, public_inputs_bytes, proof_blobs, seed: Optional[int] = None,
-                       stats: Optional[dict] = None) -> list:
-    """batch_verify on what a prover sends: proof_blobs[i] a serialized `Proof` (transcript.serialize_proof), public_inputs_bytes[i] its
-    public inputs, 32 bytes each.  Proofs and inputs are decoded on the device (codec.proofs_from_bytes_dev, plonk_fr_from_bytes_dev) and the
-    records go to plonk_verify_batch_dev where they are.  A proof that does not decode is rejected without touching the others; `stats`
-    receives "decode_status" beside batch_verify's "pairing_checks" and "status"."""
-    from . import codec
-    curve = worker.curve_name
-    if open_key.curve != curve:
-        raise ValueError("open key and worker are on different curves")
-    K = len(proof_blobs)
-    if len(public_inputs_bytes) != K:
-        raise ValueError("one public-input blob per proof")
-    pubs = [bytes(p) for p in public_inputs_bytes]
-    if any(len(p) % 32 or len(p) != len(pubs[0]) for p in pubs):
-        raise ValueError("every proof of a batch needs the same number of public inputs, 32 bytes each")
-    num_inputs = len(pubs[0]) // 32 if K else 0
-    if K == 0:
-        if stats is not None:
-            stats.update(pairing_checks=0, status=[], decode_status=[])
-        return []
-    rho = _rhos(curve, K, seed)
-    d_recs, decode = codec.proofs_from_bytes_dev(worker, proof_blobs)
-    bufs = [d_recs]                              # everything allocated below is freed on every exit
-    alloc = lambda nbytes: bufs.append(worker.alloc(nbytes)) or bufs[-1]
-    try:
-        d_pub = None
-        if num_inputs:
-            raw = np.frombuffer(b"".join(pubs), dtype=np.uint8)
-            d_raw = alloc(raw.nbytes).upload(raw)
-            d_pub = alloc(K * num_inputs * 32)
-            d_st = alloc(K * num_inputs * 4)
-            worker.memset_dev(d_st.ptr, 0, K * num_inputs * 4)
-            worker.fr_from_bytes_dev(d_raw.ptr, 32, K * num_inputs, d_pub.ptr, 4, d_st.ptr, 1)
-            decode = decode | np.bitwise_or.reduce(d_st.download((K, num_inputs), dtype=np.uint32), axis=1)
-        pts, status, _ = device_verify_records(worker, vk, num_inputs, K, d_recs.ptr, d_pub.ptr if d_pub else 0, rho)
-    finally:
-        for b in bufs:
-            b.free()
-    verdict, checks = _bisect(worker, open_key, pts, [i for i in range(K) if decode[i] == 0 and status[i] == 0])
-    if stats is not None:
-        stats["pairing_checks"] = checks
-        stats["status"] = [int(s) for s in status]
-        stats["decode_status"] = [int(s) for s in decode]
-    return verdict
-
-
-def verify(worker, vk: dict, open_key: OpenKey, public_inputs, proof: dict, stats: Optional[dict] = None) -> bool:
-    """One proof, the single check of jf-plonk's verify (rho = 1)."""
-    one = _fr.FIELDS[worker.curve_name].to_limbs(1)[None, :]
-    return batch_verify(worker, vk, open_key, [public_inputs], [proof], stats=stats, _rho=one)[0]
 
 
 def check_srs(worker, open_key: OpenKey, count: int, seed: Optional[int] = None) -> bool:
@@ -359,7 +310,7 @@ def check_srs(worker, open_key: OpenKey, count: int, seed: Optional[int] = None)
     return pairing_check(curve, [s1, _g1_neg(curve, s0)], [open_key.h, open_key.beta_h])
 
 
-# ------------------------------------------------------------------------------------------------ a key per proof, folded on the device
+# ------------------------------------------------------------------------------------------------ a key per proof
 MULTI_STATUS_BITS = {**STATUS_BITS, 32: "key index out of range", 64: "public-input span out of range or of the wrong length"}
 MAX_KEYS = 4096
 
@@ -436,78 +387,21 @@ def device_verify_multi(worker, keys: VerifyKeySet, vk_index, public_inputs_list
     if len(public_inputs_list) != K or len(vk_index) != K or rho.shape[0] != K:
         raise ValueError("one key index, one public-input list and one rho per proof")
     pis = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 4) for p in public_inputs_list]
-    bufs = []
-    try:
-        ptrs = _upload_batch(worker, bufs, vk_index, pis, proofs, _offsets)
-        return _multi_records(worker, keys, K, *ptrs, rho, debug)[:3]
-    finally:
-        for b in bufs:
-            b.free()
+    with _Buffers(worker) as bufs:
+        launch = _multi_launch(worker, keys, K, *_upload_multi(bufs, vk_index, pis, proofs, _offsets))
+        return _download_pairs(K, *_launch_pairs(bufs, K, rho, debug, launch))
 
 
-def _upload_batch(worker, bufs: list, vk_index, pis, proofs, offsets=None):
-    """Records, key indices, offsets and the concatenated public inputs of a batch on the device: (d_recs, d_idx, d_pub, d_off, pub_total),
-    0 for an empty array.  The buffers are appended to bufs as they are allocated, for the caller to free."""
-    curve = worker.curve_name
-    K = len(proofs)
-    recs = np.stack([proof_record(curve, p) for p in proofs]) if K else np.zeros((0, 2 * _q64(curve) * NPTS + 4 * NEVALS), np.uint64)
-    pub = np.concatenate(pis + [np.zeros((0, 4), np.uint64)])
+def _upload_multi(bufs: _Buffers, vk_index, pis, proofs, offsets=None):
+    """_upload_batch with the key indices and the K + 1 offsets of the ragged public-input list: (d_recs, d_idx, d_pub, d_off, pub_total)."""
     off = np.concatenate([[0], np.cumsum([p.shape[0] for p in pis])]).astype(np.uint64) if offsets is None else np.asarray(offsets, dtype=np.uint64)
-    if off.shape != (K + 1,):
+    if off.shape != (len(proofs) + 1,):
         raise ValueError("K + 1 offsets")
-    ptrs = []
-    for arr in (recs, np.asarray(vk_index, dtype=np.uint32), pub, off):
-        if arr.nbytes:
-            bufs.append(worker.alloc(arr.nbytes))
-            bufs[-1].upload(arr)
-        ptrs.append(bufs[-1].ptr if arr.nbytes else 0)
-    return (*ptrs, pub.shape[0])
+    d_recs, d_pub, d_idx, d_off = _upload_batch(bufs, proofs, pis, np.asarray(vk_index, dtype=np.uint32), off)
+    return d_recs, d_idx, d_pub, d_off, sum(p.shape[0] for p in pis)
 
 
-def _multi_records(worker, keys: VerifyKeySet, K: int, d_recs: int, d_idx: int, d_pub: int, d_off: int, pub_total: int, rho: np.ndarray,
-                   debug: bool = False, extra_mask: Optional[np.ndarray] = None, tree: bool = False, kernel_ms: Optional[dict] = None):
-    """The device part on buffers already there: (points, status, debug, d_tree).  With tree=True the sum tree over the output pairs, masked
-    by the status words (OR extra_mask), stays on the device in d_tree (a DeviceBuffer the caller frees); None otherwise.  kernel_ms (a
-    dict) receives the device time of the two entry points, "verify" and "tree" (plonk_last_kernel_ms: each read waits for its kernels)."""
-    n64 = _q64(worker.curve_name)
-    bufs = []
-    alloc = lambda nbytes: bufs.append(worker.alloc(max(nbytes, 8))) or bufs[-1]
-    d_tree = None
-    try:
-        d_rho = alloc(rho.nbytes).upload(np.ascontiguousarray(rho, dtype=np.uint64))
-        d_out = alloc(K * 2 * 2 * n64 * 8)
-        d_status = alloc(K * 4)
-        d_dbg = alloc(K * 9 * 32) if debug else None
-        if debug:
-            worker.memset_dev(d_dbg.ptr, 0, K * 9 * 32)
-        worker.verify_batch_multi_dev(keys.keys, keys.n_vks, K, d_recs, d_idx, d_pub if pub_total else 0, d_off, pub_total, d_rho.ptr, d_out.ptr, d_status.ptr,
-                                      d_dbg.ptr if debug else 0)
-        if kernel_ms is not None and K:
-            kernel_ms["verify"] = worker.last_kernel_ms()
-        status = None
-        if tree and K:
-            d_mask = d_status
-            if extra_mask is not None:
-                status = d_status.download((K,), dtype=np.uint32)
-                d_mask = alloc(K * 4).upload(np.ascontiguousarray(status | extra_mask, dtype=np.uint32))
-            d_tree = worker.alloc((2 * tree_leaves(K) - 1) * 2 * 2 * n64 * 8)
-            worker.g1_sum_tree_dev(d_out.ptr, K, d_mask.ptr, d_tree.ptr)
-            if kernel_ms is not None:
-                kernel_ms["tree"] = worker.last_kernel_ms()
-        pts = d_out.download((K, 2, 2 * n64))
-        if status is None:
-            status = d_status.download((K,), dtype=np.uint32)
-        dbg = d_dbg.download((K, 9, 4)) if debug else None
-    except BaseException:
-        if d_tree is not None:
-            d_tree.free()
-        raise
-    finally:
-        for b in bufs:
-            b.free()
-    return pts, status, dbg, d_tree
-
-
+# ------------------------------------------------------------------------------------------------ the fold on the device, and the batch functions
 def tree_leaves(K: int) -> int:
     """P of `plonk_g1_sum_tree_dev`: the next power of two >= K (1 for K <= 1)."""
     return 1 << max(K - 1, 0).bit_length()
@@ -521,15 +415,11 @@ def g1_sum_tree(worker, points: np.ndarray, mask: Optional[np.ndarray] = None) -
     if K == 0:
         worker.g1_sum_tree_dev(0, 0, 0, 0)
         return np.zeros((0, 2, 2 * n64), np.uint64)
-    bufs = [worker.alloc(points.nbytes).upload(points), worker.alloc((2 * tree_leaves(K) - 1) * 4 * n64 * 8)]
-    try:
-        if mask is not None:
-            bufs.append(worker.alloc(K * 4).upload(np.ascontiguousarray(mask, dtype=np.uint32).reshape(K)))
-        worker.g1_sum_tree_dev(bufs[0].ptr, K, bufs[2].ptr if mask is not None else 0, bufs[1].ptr)
-        return bufs[1].download((2 * tree_leaves(K) - 1, 2, 2 * n64))
-    finally:
-        for b in bufs:
-            b.free()
+    with _Buffers(worker) as bufs:
+        d_mask = bufs.upload(np.ascontiguousarray(mask, dtype=np.uint32).reshape(K)) if mask is not None else 0
+        d_tree = bufs.alloc((2 * tree_leaves(K) - 1) * 4 * n64 * 8)
+        worker.g1_sum_tree_dev(bufs.upload(points), K, d_mask, d_tree.ptr)
+        return d_tree.download((2 * tree_leaves(K) - 1, 2, 2 * n64))
 
 
 def bisect_tree(P: int, live: Sequence[bool], holds) -> tuple:
@@ -585,100 +475,127 @@ def _bisect_on_device_tree(worker, open_key: OpenKey, d_tree, K: int, live: Sequ
     return bisect_tree(tree_leaves(K), live, holds)
 
 
+def _fold(bufs: _Buffers, open_key: OpenKey, K: int, rho: np.ndarray, launch, decode: Optional[np.ndarray], stats: Optional[dict]) -> list:
+    """The fold of every batch function, and the one place that fills `stats`: the per-proof pairs (_launch_pairs), the sum tree over
+    them (`plonk_g1_sum_tree_dev`) masked by the status words — ORed with the decode words of the bytes route, where a proof that did not
+    decode has to stay out of every sum —, and the bisection over its nodes.  Only status words and tree nodes are read back, never the K
+    pairs.  An empty batch launches nothing.  "kernel_ms" is the device time of the two entry points (plonk_last_kernel_ms: each read
+    waits for its kernels, so it is read only when stats are asked for)."""
+    worker = bufs.worker
+    status, verdict, checks = np.zeros((0,), np.uint32), [], 0
+    kms = {} if stats is not None else None
+    if K:
+        d_out, d_status, _ = _launch_pairs(bufs, K, rho, False, launch)
+        if kms is not None:
+            kms["verify"] = worker.last_kernel_ms()
+        d_mask, mask = d_status, None
+        if decode is not None:
+            status = d_status.download((K,), dtype=np.uint32)
+            mask = status | decode
+            d_mask = bufs.alloc(K * 4).upload(mask)
+        d_tree = bufs.alloc((2 * tree_leaves(K) - 1) * 2 * 2 * _q64(worker.curve_name) * 8)
+        worker.g1_sum_tree_dev(d_out.ptr, K, d_mask.ptr, d_tree.ptr)
+        if kms is not None:
+            kms["tree"] = worker.last_kernel_ms()
+        if mask is None:                                      # the tree is masked by the status words where they are: read them behind it
+            mask = status = d_status.download((K,), dtype=np.uint32)
+        verdict, checks = _bisect_on_device_tree(worker, open_key, d_tree, K, [m == 0 for m in mask])
+    if stats is not None:
+        stats["pairing_checks"] = checks
+        stats["status"] = [int(s) for s in status]
+        stats["kernel_ms"] = kms
+        if decode is not None:
+            stats["decode_status"] = [int(s) for s in decode]
+    return verdict
+
+
+def _curve(worker, open_key: OpenKey) -> str:
+    if open_key.curve != worker.curve_name:
+        raise ValueError("open key and worker are on different curves")
+    return worker.curve_name
+
+
+def batch_verify(worker, vk: dict, open_key: OpenKey, public_inputs_list, proofs, seed: Optional[int] = None, stats: Optional[dict] = None,
+                 _rho: Optional[np.ndarray] = None) -> list:
+    """One verdict per proof, all proofs under one verifying key with the same number of public inputs (another count is a ValueError).
+    `stats` (a dict, optional) receives "pairing_checks", the status word of every proof ("status") and "kernel_ms" (the device time of
+    the two entry points, "verify" and "tree")."""
+    curve = _curve(worker, open_key)
+    K = len(proofs)
+    rho = _rhos(curve, K, seed) if _rho is None else _rho
+    pis, num_inputs = _one_key_inputs(K, public_inputs_list, rho)
+    with _Buffers(worker) as bufs:
+        d_recs, d_pub = _upload_batch(bufs, proofs, pis)
+        return _fold(bufs, open_key, K, rho, _one_key_launch(bufs, vk, num_inputs, K, d_recs, d_pub), None, stats)
+
+
+def batch_verify_bytes(worker, vk: dict, open_key: OpenKey, public_inputs_bytes, proof_blobs, seed: Optional[int] = None,
+                       stats: Optional[dict] = None) -> list:
+    """batch_verify on what a prover sends: proof_blobs[i] a serialized `Proof` (transcript.serialize_proof), public_inputs_bytes[i] its
+    public inputs, 32 bytes each.  Proofs and inputs are decoded on the device (_decode_batch) and the records go to plonk_verify_batch_dev
+    where they are.  A proof or an input that does not decode masks its proof out of the fold and rejects it without touching the others;
+    `stats` receives "decode_status" beside batch_verify's "pairing_checks", "status" and "kernel_ms"."""
+    curve = _curve(worker, open_key)
+    K = len(proof_blobs)
+    if len(public_inputs_bytes) != K:
+        raise ValueError("one public-input blob per proof")
+    pubs = [bytes(p) for p in public_inputs_bytes]
+    if any(len(p) % 32 or len(p) != len(pubs[0]) for p in pubs):
+        raise ValueError("every proof of a batch needs the same number of public inputs, 32 bytes each")
+    num_inputs = len(pubs[0]) // 32 if K else 0
+    with _Buffers(worker) as bufs:
+        d_recs, d_pub, _, decode = _decode_batch(bufs, pubs, proof_blobs)
+        launch = _one_key_launch(bufs, vk, num_inputs, K, d_recs, d_pub) if K else None     # an empty batch does not look at the key
+        return _fold(bufs, open_key, K, _rhos(curve, K, seed), launch, decode, stats)
+
+
+def verify(worker, vk: dict, open_key: OpenKey, public_inputs, proof: dict, stats: Optional[dict] = None) -> bool:
+    """One proof, the single check of jf-plonk's verify (rho = 1)."""
+    one = _fr.FIELDS[worker.curve_name].to_limbs(1)[None, :]
+    return batch_verify(worker, vk, open_key, [public_inputs], [proof], stats=stats, _rho=one)[0]
+
+
 def batch_verify_multi(worker, keys, open_key: OpenKey, vk_index, public_inputs_list, proofs, seed: Optional[int] = None,
                        stats: Optional[dict] = None, _rho: Optional[np.ndarray] = None) -> list:
     """jf-plonk's batch_verify: one verdict per proof, proof j checked under keys[vk_index[j]] (a VerifyKeySet, or a list of key dicts
-    wrapped and closed here) with public_inputs_list[j].  The device computes every proof's pair (`plonk_verify_batch_multi_dev`) and folds
-    the batch into a sum tree (`plonk_g1_sum_tree_dev`, masked by the status words); the host pairs the root and, if that fails, bisects over
-    tree nodes read back one at a time (bisect_tree) — no point addition on the host.  `stats` receives "pairing_checks", "status" and
-    "kernel_ms" (the device time of the two entry points)."""
-    curve = worker.curve_name
-    if open_key.curve != curve:
-        raise ValueError("open key and worker are on different curves")
+    wrapped and closed here) with public_inputs_list[j].  A key index out of range and a list of another length than its key's count are
+    verdicts (status 32 / 64), not errors.  `stats` receives "pairing_checks", "status" and "kernel_ms" as batch_verify's does."""
+    curve = _curve(worker, open_key)
     K = len(proofs)
     if len(vk_index) != K or len(public_inputs_list) != K:
         raise ValueError("one key index and one public-input list per proof")
     pis = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 4) for p in public_inputs_list]
     keyset, owned = _key_set(worker, keys, vk_index, pis)
-    bufs, d_tree = [], None
-    kms = {} if stats is not None else None
     try:
-        if K == 0:
-            status, verdict, checks = np.zeros((0,), np.uint32), [], 0
-        else:
+        with _Buffers(worker) as bufs:
             rho = _rhos(curve, K, seed) if _rho is None else _rho
-            ptrs = _upload_batch(worker, bufs, vk_index, pis, proofs)
-            _, status, _, d_tree = _multi_records(worker, keyset, K, *ptrs, rho, tree=True, kernel_ms=kms)
-            verdict, checks = _bisect_on_device_tree(worker, open_key, d_tree, K, [s == 0 for s in status])
+            return _fold(bufs, open_key, K, rho, _multi_launch(worker, keyset, K, *_upload_multi(bufs, vk_index, pis, proofs)), None, stats)
     finally:
-        for b in bufs + [d_tree]:
-            if b:
-                b.free()
         if owned:
             keyset.close()
-    if stats is not None:
-        stats["pairing_checks"] = checks
-        stats["status"] = [int(s) for s in status]
-        stats["kernel_ms"] = kms
-    return verdict
 
 
 def batch_verify_multi_bytes(worker, keys, open_key: OpenKey, vk_index, public_inputs_bytes, proof_blobs, seed: Optional[int] = None,
                              stats: Optional[dict] = None) -> list:
     """batch_verify_multi on what provers send: proof_blobs[j] a serialized `Proof`, public_inputs_bytes[j] its public inputs, 32 bytes each
-    and as many as ITS circuit has (blobs of different lengths; one that is no multiple of 32 bytes is a ValueError).  Proofs are decoded by
-    codec.proofs_from_bytes_dev and all inputs by ONE plonk_fr_from_bytes_dev launch over their concatenation; a proof or an input that does
-    not decode masks its proof out of the fold and rejects it without touching the others.  `stats` receives "decode_status" beside
-    "pairing_checks" and "status"."""
-    from . import codec
-    curve = worker.curve_name
-    if open_key.curve != curve:
-        raise ValueError("open key and worker are on different curves")
+    and as many as ITS circuit has (blobs of different lengths; one that is no multiple of 32 bytes is a ValueError).  Decoded on the device
+    as in batch_verify_bytes, which is this with spans of one length; `stats` receives "decode_status" beside "pairing_checks", "status"
+    and "kernel_ms"."""
+    curve = _curve(worker, open_key)
     K = len(proof_blobs)
     if len(public_inputs_bytes) != K or len(vk_index) != K:
         raise ValueError("one key index and one public-input blob per proof")
     pubs = [bytes(p) for p in public_inputs_bytes]
     if any(len(p) % 32 for p in pubs):
         raise ValueError("public inputs are 32 bytes each")
-    counts = [len(p) // 32 for p in pubs]
-    keyset, owned = _key_set(worker, keys, vk_index, [np.zeros((c, 4), np.uint64) for c in counts])
-    bufs, d_tree = [], None
-    kms = {} if stats is not None else None
-    alloc = lambda nbytes: bufs.append(worker.alloc(nbytes)) or bufs[-1]
+    keyset, owned = _key_set(worker, keys, vk_index, [np.zeros((len(p) // 32, 4), np.uint64) for p in pubs])
     try:
-        if K == 0:
-            status, decode, verdict, checks = np.zeros((0,), np.uint32), np.zeros((0,), np.uint32), [], 0
-        else:
-            rho = _rhos(curve, K, seed)
-            d_recs, decode = codec.proofs_from_bytes_dev(worker, proof_blobs)
-            bufs.append(d_recs)
-            off = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
-            total = int(off[-1])
-            d_idx = alloc(K * 4).upload(np.asarray(vk_index, dtype=np.uint32))
-            d_off = alloc((K + 1) * 8).upload(off)
-            d_pub = None
-            if total:
-                raw = np.frombuffer(b"".join(pubs), dtype=np.uint8)
-                d_raw = alloc(raw.nbytes).upload(raw)
-                d_pub = alloc(total * 32)
-                d_st = alloc(total * 4)
-                worker.memset_dev(d_st.ptr, 0, total * 4)
-                worker.fr_from_bytes_dev(d_raw.ptr, 32, total, d_pub.ptr, 4, d_st.ptr, 1)
-                st = d_st.download((total,), dtype=np.uint32)
-                decode = decode | np.array([np.bitwise_or.reduce(st[int(off[j]):int(off[j + 1])], initial=0) for j in range(K)], dtype=np.uint32)
-            decode = np.ascontiguousarray(decode, dtype=np.uint32)
-            _, status, _, d_tree = _multi_records(worker, keyset, K, d_recs.ptr, d_idx.ptr, d_pub.ptr if d_pub else 0, d_off.ptr, total, rho,
-                                                  extra_mask=decode, tree=True, kernel_ms=kms)
-            verdict, checks = _bisect_on_device_tree(worker, open_key, d_tree, K, [s == 0 and d == 0 for s, d in zip(status, decode)])
+        with _Buffers(worker) as bufs:
+            d_recs, d_pub, off, decode = _decode_batch(bufs, pubs, proof_blobs)
+            d_idx, d_off = bufs.upload(np.asarray(vk_index, dtype=np.uint32)), bufs.upload(off)
+            launch = _multi_launch(worker, keyset, K, d_recs, d_idx, d_pub, d_off, int(off[-1]))
+            return _fold(bufs, open_key, K, _rhos(curve, K, seed), launch, decode, stats)
     finally:
-        for b in bufs + [d_tree]:
-            if b:
-                b.free()
         if owned:
             keyset.close()
-    if stats is not None:
-        stats["pairing_checks"] = checks
-        stats["status"] = [int(s) for s in status]
-        stats["decode_status"] = [int(s) for s in decode]
-        stats["kernel_ms"] = kms
-    return verdict
+

@@ -541,6 +541,12 @@ class PlonkWorker:
         """k serialized proofs -> k records of plonk_verify_batch_dev and k status words (plonk_proofs_from_bytes_dev).  Enqueued, not synchronised."""
         check(self.lib.plonk_proofs_from_bytes_dev(self.ctx, d_bytes or None, k, d_proofs or None, d_status or None))
 
+    def verify_batch_dev(self, key, k: int, d_proofs: int, d_pub_inputs: int, d_rho: int, d_out_points: int, d_status: int, d_debug: int = 0):
+        """k proofs under one key (an _ffi.VerifyKey whose d_comms points at its 18 commitments), k x key.num_inputs public inputs
+        (plonk_verify_batch_dev).  Enqueued, not synchronised."""
+        check(self.lib.plonk_verify_batch_dev(self.ctx, C.byref(key), k, d_proofs or None, d_pub_inputs or None, d_rho or None, d_out_points or None,
+                                              d_status or None, d_debug or None))
+
     def verify_batch_multi_dev(self, keys, n_vks: int, k: int, d_proofs: int, d_vk_index: int, d_pub_inputs: int, d_pub_offsets: int, pub_total: int,
                                d_rho: int, d_out_points: int, d_status: int, d_debug: int = 0):
         """k proofs, proof j under keys[vk_index[j]] (a ctypes array of _ffi.VerifyKey) on its span of a ragged public-input list

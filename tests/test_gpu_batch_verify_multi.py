@@ -169,7 +169,7 @@ def _off_curve(pt):
 
 
 @pytest.mark.parametrize("curve,cid", CURVES)
-def test_one_key_equals_the_single_key_entry_point(gpu_workers, oracle, curve, cid):
+def test_one_key_equals_the_single_key_entry_point(gpu_workers, oracle, monkeypatch, curve, cid):
     w, keys, cases = _setup(gpu_workers, oracle, curve, cid)
     f = _fr.FIELDS[curve]
     vk, pub = keys[0], cases[0]["pub"]
@@ -186,10 +186,14 @@ def test_one_key_equals_the_single_key_entry_point(gpu_workers, oracle, curve, c
         assert np.array_equal(st_new, st_old) and np.array_equal(pts_new, pts_old)
         key = VF.OpenKey.from_trapdoor(curve, TAU)
         st, st_m = {}, {}
-        want = VF.batch_verify(w, vk, key, [pub] * K, prfs, stats=st, _rho=rho)
+        with monkeypatch.context() as m:                   # the fold is the device's: no point addition through the host
+            m.setattr(w, "g1_add", lambda *a: pytest.fail("batch_verify added points on the host"))
+            want = VF.batch_verify(w, vk, key, [pub] * K, prfs, stats=st, _rho=rho)
         assert want == [True, False, True, False, True]
         assert VF.batch_verify_multi(w, ks, key, [0] * K, [pub] * K, prfs, stats=st_m, _rho=rho) == want
         assert st_m["status"] == st["status"]
+        assert st["pairing_checks"] == st_m["pairing_checks"]
+        assert set(st["kernel_ms"]) == set(st_m["kernel_ms"]) == {"verify", "tree"}
 
 
 # ------------------------------------------------------------------------------------------------ verdicts

@@ -1,8 +1,9 @@
 """Verifying what a prover sends: four proofs of a 2^10-gate instance serialized with transcript.serialize_proof, their public inputs as 32-byte
 scalars, and the open key as bytes, through verifier.batch_verify_bytes — decoded on the device (plonk_proofs_from_bytes_dev) and handed to
-plonk_verify_batch_dev as device records.  All four accepted with one pairing check; a flipped sign bit is the verifier's rejection (decode
-status 0), an x without a point the codec's (decode status 1); neither disturbs the other proofs; the verdicts are those of batch_verify on the
-dicts proof_from_bytes returns."""
+plonk_verify_batch_dev as device records, the output pairs folded into the device's sum tree masked by status and decode words.  All four
+accepted with one pairing check; a flipped sign bit is the verifier's rejection (decode status 0), an x without a point the codec's (decode
+status 1); neither disturbs the other proofs, and the pairing checks are those verifier.bisect_tree counts for the same leaves, in a batch of
+four and in one of three with a padded leaf; the verdicts are those of batch_verify on the dicts proof_from_bytes returns."""
 import pytest
 
 from distributed_plonk_amd import codec as CD
@@ -32,14 +33,23 @@ def test_batch_verify_bytes(gpu_workers, oracle, curve, cid):
     assert st["pairing_checks"] == 1 and st["decode_status"] == [0] * K and st["status"] == [0] * K
 
     nb = R.NBYTES[curve]
-    flipped = bytearray(blobs[2])
-    flipped[point_at(curve, 1) + nb - 1] ^= 0x80                          # -[w_1]: a point of the curve, not the prover's
+    sign = point_at(curve, 1) + nb - 1
+    flip = lambda blob: blob[:sign] + bytes([blob[sign] ^ 0x80]) + blob[sign + 1:]       # -[w_1]: a point of the curve, not the prover's
     at = point_at(curve, 8)
     no_point = blobs[1][:at] + no_point_x(curve) + blobs[1][at + nb:]
-    bad = [blobs[0], no_point, bytes(flipped), blobs[3]]
+    bad = [blobs[0], no_point, flip(blobs[2]), blobs[3]]
     got = VF.batch_verify_bytes(w, vk, key, [pub_bytes] * K, bad, seed=2, stats=st)
     assert got == [True, False, False, True]
     assert st["decode_status"] == [0, 1, 0, 0] and st["status"][2] == 0
+    # the pairing checks are those of the bisection over a tree of four leaves [live, masked, bad, live]: the sums that contain leaf 2 fail
+    want, checks = VF.bisect_tree(4, [True, False, True, True], lambda node: node not in (0, 2, 3 + 2))
+    assert want == got and st["pairing_checks"] == checks == 4
+
+    # three proofs, the wrong one in the middle: a padded fourth leaf, nothing masked by the decoder, and a bisection
+    got = VF.batch_verify_bytes(w, vk, key, [pub_bytes] * 3, [blobs[0], flip(blobs[1]), blobs[2]], seed=4, stats=st)
+    want, checks = VF.bisect_tree(4, [True] * 3, lambda node: node not in (0, 1, 3 + 1))
+    assert got == want == [True, False, True] and st["pairing_checks"] == checks == 4
+    assert st["decode_status"] == [0] * 3 and st["status"] == [0] * 3
 
     # the same verdicts from batch_verify on the decoded dicts (the proof that does not decode has none)
     dicts = [CD.proof_from_bytes(w, b) for i, b in enumerate(bad) if i != 1]
