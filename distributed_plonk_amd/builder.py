@@ -50,7 +50,7 @@ import numpy as np
 from . import circuit as _circuit
 from . import fr as _fr
 from .synthetic import NUM_SELECTORS, NUM_WIRE_TYPES
-from .worker import REPLAY_FUSE_DEFAULT, PlonkWorker
+from .worker import REPLAY_FUSE_DEFAULT, DeviceScope, PlonkWorker, closing_on_error
 
 SELECTOR_INDEX = {**{f"q_lc{i}": i for i in range(4)}, "q_mul0": 4, "q_mul1": 5, **{f"q_hash{i}": 6 + i for i in range(4)}, "q_o": 10, "q_c": 11}
 GIVEN = 0xFFFFFFFF                                    # def_gate of a variable no gate defines
@@ -97,19 +97,14 @@ class BuiltCircuit:
         if self._dev is not None and self._dev[0] is not worker:
             self.close()
         if self._dev is None:
-            bufs = []
-            try:
-                for a in (self.wire_vars, self.selector_evals, self.def_gate) + ((self.hint_op,) if self.has_hints else ()):
-                    bufs.append(worker.alloc(a.nbytes).upload(a))
-            except BaseException:
-                for b in bufs:
-                    b.free()
-                raise
-            self._dev = (worker, bufs)
+            with DeviceScope(worker) as s:
+                bufs = [s.upload(a) for a in (self.wire_vars, self.selector_evals, self.def_gate) + ((self.hint_op,) if self.has_hints else ())]
+                self._dev = (worker, [s.release(b) for b in bufs])
         return self._dev[1]
 
     def close(self):
-        """Free the device copy of the circuit that solve_dev keeps between calls."""
+        """Free the device copy of the circuit that solve_dev keeps between calls.  _upload, _input_vars_dev and schedule each released theirs to
+        this object when they had filled them, so they are freed one by one here."""
         if self._dev is not None:
             for b in self._dev[1]:
                 b.free()
@@ -124,7 +119,8 @@ class BuiltCircuit:
     def _input_vars_dev(self, worker: PlonkWorker):
         if self._dev_input_vars is None:
             ids = np.ascontiguousarray(self.input_vars, dtype=np.uint32)
-            self._dev_input_vars = worker.alloc(max(4, ids.nbytes)).upload(ids)
+            with DeviceScope(worker) as s:
+                self._dev_input_vars = s.release(s.alloc(max(4, ids.nbytes)).upload(ids))
         return self._dev_input_vars
 
     def schedule(self, worker: PlonkWorker) -> "SolveSchedule":
@@ -134,16 +130,13 @@ class BuiltCircuit:
             raise ValueError(f"circuit over {self.curve}, worker over {worker.curve_name}")
         d_vars, d_sel, d_def, *d_hint = self._upload(worker)
         if self._schedule is None:
-            d_order = worker.alloc(self.n * 4)
-            try:
+            with DeviceScope(worker) as s:
+                d_order = s.alloc(self.n * 4)
                 unsolved, levels, evaluations, seg = worker.circuit_schedule_dev(d_vars.ptr, self.n, self.num_vars, d_sel.ptr, d_def.ptr,
                                                                                  d_hint[0].ptr if d_hint else 0, d_order.ptr)
                 if unsolved >= 0:
                     raise _circuit.UnsolvableCircuit(unsolved)
-            except BaseException:
-                d_order.free()
-                raise
-            self._schedule = SolveSchedule(d_order, seg, levels, evaluations)
+                self._schedule = SolveSchedule(s.release(d_order), seg, levels, evaluations)
         return self._schedule
 
     def solve_many_dev(self, worker: PlonkWorker, inputs=None, public_inputs=None, *, d_inputs: Optional[int] = None, fuse_width: Optional[int] = None,
@@ -181,7 +174,7 @@ class BuiltCircuit:
         sched = self.schedule(worker)
         d_vars, d_sel, _, *d_hint = self._upload(worker)
         out = SolvedBatch(worker, self, K, d_vars.ptr, d_sel.ptr)
-        try:
+        with closing_on_error(out):
             if d_inputs is None:
                 witness = np.zeros((K, self.num_vars, 4), dtype=np.uint64)
                 if num_in:
@@ -197,9 +190,6 @@ class BuiltCircuit:
                 out.d_pub.upload(pub)
             worker.circuit_replay_dev(d_vars.ptr, self.n, self.num_vars, d_sel.ptr, d_hint[0].ptr if d_hint else 0, sched.d_order.ptr, sched.seg, sched.levels,
                                       out.d_pub.ptr if self.num_public else 0, self.num_public, out.d_witness.ptr, K, fuse_width)
-        except BaseException:
-            out.close()
-            raise
         return out
 
     def setup(self, worker: PlonkWorker, k: Optional[np.ndarray] = None) -> _circuit.CircuitKey:
@@ -229,7 +219,7 @@ class BuiltCircuit:
         d_vars, d_sel, d_def, *d_hint = self._upload(worker)
         n = self.n
         out = SolvedWitness(worker, self, d_vars.ptr, d_sel.ptr)
-        try:
+        with closing_on_error(out):
             if d_inputs is None:
                 witness = np.zeros((self.num_vars, 4), dtype=np.uint64)
                 witness[self.input_vars] = inp
@@ -249,9 +239,6 @@ class BuiltCircuit:
                                                                                  out.d_witness.ptr)
             if unsolved >= 0:
                 raise _circuit.UnsolvableCircuit(unsolved)
-        except BaseException:
-            out.close()
-            raise
         return out
 
     def preprocess(self, worker: PlonkWorker, inputs=None, public_inputs=None, check: bool = True, k: Optional[np.ndarray] = None, *,
@@ -281,20 +268,15 @@ class SolvedWitness:
     def __init__(self, worker: PlonkWorker, built: BuiltCircuit, d_wire_vars: int, d_selector_evals: int):
         self.built, self.d_wire_vars, self.d_selector_evals = built, d_wire_vars, d_selector_evals
         self.levels = self.evaluations = 0
-        self.d_witness = worker.alloc(built.num_vars * 32)
-        try:
-            self.d_pub = worker.alloc(built.n * 32)
-        except BaseException:
-            self.d_witness.free()
-            raise
+        self._scope = DeviceScope(worker)
+        with closing_on_error(self._scope):
+            self.d_witness, self.d_pub = self._scope.alloc(built.num_vars * 32), self._scope.alloc(built.n * 32)
 
     def witness(self) -> np.ndarray:
         return self.d_witness.download((self.built.num_vars, 4))
 
     def close(self):
-        for b in (self.d_witness, self.d_pub):
-            if b.ptr:
-                b.free()
+        self._scope.close()
 
 
 class SolveSchedule:
@@ -316,12 +298,9 @@ class SolvedBatch:
 
     def __init__(self, worker: PlonkWorker, built: BuiltCircuit, K: int, d_wire_vars: int, d_selector_evals: int):
         self.built, self.K, self.d_wire_vars, self.d_selector_evals = built, K, d_wire_vars, d_selector_evals
-        self.d_witness = worker.alloc(K * built.num_vars * 32)
-        try:
-            self.d_pub = worker.alloc(max(8, K * built.num_public * 32))
-        except BaseException:
-            self.d_witness.free()
-            raise
+        self._scope = DeviceScope(worker)
+        with closing_on_error(self._scope):
+            self.d_witness, self.d_pub = self._scope.alloc(K * built.num_vars * 32), self._scope.alloc(max(8, K * built.num_public * 32))
 
     def witness(self, b: int) -> np.ndarray:
         """witness b -> (num_vars, 4); waits for the solve"""
@@ -330,9 +309,7 @@ class SolvedBatch:
         return self.d_witness.download((self.built.num_vars, 4), byte_offset=b * self.built.num_vars * 32)
 
     def close(self):
-        for b in (self.d_witness, self.d_pub):
-            if b.ptr:
-                b.free()
+        self._scope.close()
 
 
 class CircuitBuilder:

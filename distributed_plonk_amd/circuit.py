@@ -23,7 +23,7 @@ import numpy as np
 
 from . import fr as _fr
 from .synthetic import NUM_SELECTORS, NUM_WIRE_TYPES, wire_subset_separators
-from .worker import PlonkWorker
+from .worker import DeviceScope, PlonkWorker, closing_on_error
 
 
 class UnsatisfiedCircuit(ValueError):
@@ -122,22 +122,19 @@ class PreprocessedCircuit:
         self.w, self.n, self.num_inputs = worker, n, num_inputs
         self.log_n = n.bit_length() - 1
         self.k = np.ascontiguousarray(k, dtype=np.uint64)
-        self._bufs = []
-        alloc = lambda n_fr: self._keep(worker.alloc(n_fr * 32))
-        self.d_wires = alloc(NUM_WIRE_TYPES * n)
-        self.d_id = alloc(NUM_WIRE_TYPES * n)
-        self.d_idx = self._keep(worker.alloc(NUM_WIRE_TYPES * n * 8))
-        self.d_sig_ev = alloc(NUM_WIRE_TYPES * n)
-        self.d_sel = alloc(NUM_SELECTORS * n)
-        self.d_sig = alloc(NUM_WIRE_TYPES * n)
-        self.d_pi = alloc(n)
+        self._scope = DeviceScope(worker)
+        with closing_on_error(self._scope):
+            alloc = lambda n_fr: self._scope.alloc(n_fr * 32)
+            self.d_wires = alloc(NUM_WIRE_TYPES * n)
+            self.d_id = alloc(NUM_WIRE_TYPES * n)
+            self.d_idx = self._scope.alloc(NUM_WIRE_TYPES * n * 8)
+            self.d_sig_ev = alloc(NUM_WIRE_TYPES * n)
+            self.d_sel = alloc(NUM_SELECTORS * n)
+            self.d_sig = alloc(NUM_WIRE_TYPES * n)
+            self.d_pi = alloc(n)
         self.wev = [self.d_wires.ptr + i * n * 32 for i in range(NUM_WIRE_TYPES)]
         self.sel_ptrs = [self.d_sel.ptr + t * n * 32 for t in range(NUM_SELECTORS)]
         self.sig_ptrs = [self.d_sig.ptr + t * n * 32 for t in range(NUM_WIRE_TYPES)]
-
-    def _keep(self, b):
-        self._bufs.append(b)
-        return b
 
     def public_inputs(self) -> np.ndarray:
         """`circuit.public_input()`: the num_inputs values (not padded) -> (num_inputs, 4)."""
@@ -152,9 +149,7 @@ class PreprocessedCircuit:
                     sigma_evals=self.d_sig_ev.download((NUM_WIRE_TYPES, n, 4)))
 
     def close(self):
-        for b in self._bufs:
-            b.free()
-        self._bufs = []
+        self._scope.close()
 
 
 def default_k(curve_name: str) -> np.ndarray:
@@ -173,7 +168,7 @@ def preprocess_dev(worker: PlonkWorker, d_wire_vars: int, n: int, num_vars: int,
     w = worker
     k = default_k(w.curve_name) if k is None else k
     inst = PreprocessedCircuit(w, n, num_inputs, k)
-    try:
+    with closing_on_error(inst):
         w.memcpy_d2d(inst.d_pi.ptr, d_pub_input, n * 32)
         w.circuit_permutation_dev(d_wire_vars, n, num_vars, inst.k, inst.d_id.ptr, inst.d_idx.ptr, inst.d_sig_ev.ptr)
         w.circuit_witness_dev(d_wire_vars, n, d_witness, num_vars, inst.d_wires.ptr)
@@ -182,23 +177,18 @@ def preprocess_dev(worker: PlonkWorker, d_wire_vars: int, n: int, num_vars: int,
             if gate >= 0 or pos >= 0:
                 raise UnsatisfiedCircuit(gate, pos, n)
         _proving_key_polys(w, n, d_selector_evals, inst.d_sig_ev.ptr, inst.d_sel.ptr, inst.d_sig.ptr)
-    except BaseException:
-        inst.close()
-        raise
     return inst
 
 
 def _proving_key_polys(w: PlonkWorker, n: int, d_selector_evals: int, d_sigma_evals: int, d_sel: int, d_sig: int):
     """proving key: selector and sigma polynomials in coefficient form (n-point iNTTs; ntt_dev consumes its input, so a copy goes in)"""
-    tmp = w.alloc(n * 32)
-    try:
+    with DeviceScope(w) as s:
+        tmp = s.alloc(n * 32)
         for src, dst, cnt in ((d_selector_evals, d_sel, NUM_SELECTORS), (d_sigma_evals, d_sig, NUM_WIRE_TYPES)):
             for t in range(cnt):
                 w.memcpy_d2d_async(tmp.ptr, src + t * n * 32, n * 32)
                 w.ntt_dev(tmp.ptr, dst + t * n * 32, n, True, False)
         w.sync()
-    finally:
-        tmp.free()
 
 
 class CircuitInstance:
@@ -209,12 +199,10 @@ class CircuitInstance:
         self.key, self.w, self.n, self.log_n, self.num_inputs, self.k = key, key.w, key.n, key.log_n, key.num_inputs, key.k
         self.d_id, self.d_idx, self.sel_ptrs, self.sig_ptrs = key.d_id, key.d_idx, key.sel_ptrs, key.sig_ptrs
         n = self.n
-        self.d_wires = self.w.alloc(NUM_WIRE_TYPES * n * 32)
-        try:
-            self.d_pi = self.w.alloc(n * 32)
-        except BaseException:
-            self.d_wires.free()
-            raise
+        self._scope = DeviceScope(self.w)
+        with closing_on_error(self._scope):
+            self.d_wires = self._scope.alloc(NUM_WIRE_TYPES * n * 32)
+            self.d_pi = self._scope.alloc(n * 32)
         self.wev = [self.d_wires.ptr + i * n * 32 for i in range(NUM_WIRE_TYPES)]
 
     def public_inputs(self) -> np.ndarray:
@@ -222,9 +210,7 @@ class CircuitInstance:
         return self.d_pi.download((self.num_inputs, 4))
 
     def close(self):
-        for b in (self.d_wires, self.d_pi):
-            if b.ptr:
-                b.free()
+        self._scope.close()
 
 
 class CircuitKey:
@@ -237,17 +223,14 @@ class CircuitKey:
         self.d_wire_vars, self.d_selector_evals = d_wire_vars, d_selector_evals
         self.log_n = n.bit_length() - 1
         self.k = np.ascontiguousarray(k, dtype=np.uint64)
-        self._bufs = []
-        try:
-            alloc = lambda nbytes: self._bufs.append(worker.alloc(nbytes)) or self._bufs[-1]
+        self._scope = DeviceScope(worker)
+        with closing_on_error(self._scope):
+            alloc = self._scope.alloc
             self.d_id = alloc(NUM_WIRE_TYPES * n * 32)
             self.d_idx = alloc(NUM_WIRE_TYPES * n * 8)
             self.d_sig_ev = alloc(NUM_WIRE_TYPES * n * 32)
             self.d_sel = alloc(NUM_SELECTORS * n * 32)
             self.d_sig = alloc(NUM_WIRE_TYPES * n * 32)
-        except BaseException:
-            self.close()
-            raise
         self.sel_ptrs = [self.d_sel.ptr + t * n * 32 for t in range(NUM_SELECTORS)]
         self.sig_ptrs = [self.d_sig.ptr + t * n * 32 for t in range(NUM_WIRE_TYPES)]
 
@@ -264,7 +247,7 @@ class CircuitKey:
             if pub.shape[0] != self.num_inputs:
                 raise ValueError(f"{pub.shape[0]} public input values for {self.num_inputs} public inputs")
         inst = CircuitInstance(self)
-        try:
+        with closing_on_error(inst):
             w.memset_dev(inst.d_pi.ptr, 0, n * 32)
             if pub is not None:
                 inst.d_pi.upload(pub)
@@ -275,9 +258,6 @@ class CircuitKey:
                 gate, pos = w.circuit_check_dev(inst.d_wires.ptr, self.d_selector_evals, inst.d_pi.ptr, self.d_idx.ptr, n)
                 if gate >= 0 or pos >= 0:
                     raise UnsatisfiedCircuit(gate, pos, n)
-        except BaseException:
-            inst.close()
-            raise
         return inst
 
     def instances(self, batch, check: bool = True):
@@ -286,9 +266,7 @@ class CircuitKey:
             yield self.instance(batch.d_witness.ptr + b * self.num_vars * 32, batch.d_pub.ptr + b * self.num_inputs * 32 if self.num_inputs else None, check)
 
     def close(self):
-        for b in self._bufs:
-            b.free()
-        self._bufs = []
+        self._scope.close()
 
 
 def setup_dev(worker: PlonkWorker, d_wire_vars: int, n: int, num_vars: int, d_selector_evals: int, num_inputs: int, k: Optional[np.ndarray] = None) -> CircuitKey:
@@ -300,12 +278,9 @@ def setup_dev(worker: PlonkWorker, d_wire_vars: int, n: int, num_vars: int, d_se
         raise ValueError(f"{num_inputs} public inputs for {n} gates")
     w = worker
     key = CircuitKey(w, d_wire_vars, n, num_vars, d_selector_evals, num_inputs, default_k(w.curve_name) if k is None else k)
-    try:
+    with closing_on_error(key):
         w.circuit_permutation_dev(d_wire_vars, n, num_vars, key.k, key.d_id.ptr, key.d_idx.ptr, key.d_sig_ev.ptr)
         _proving_key_polys(w, n, d_selector_evals, key.d_sig_ev.ptr, key.d_sel.ptr, key.d_sig.ptr)
-    except BaseException:
-        key.close()
-        raise
     return key
 
 
@@ -317,11 +292,7 @@ def preprocess(worker: PlonkWorker, circuit: Circuit, check: bool = True) -> Pre
     pub = np.zeros((n, 4), dtype=np.uint64)
     pub[:circuit.public_inputs.shape[0]] = circuit.public_inputs
     w = worker
-    bufs = []
-    try:
-        up = lambda a: bufs.append(w.alloc(max(a.nbytes, 8)).upload(a)) or bufs[-1].ptr
+    with DeviceScope(w) as s:
+        up = lambda a: s.alloc(max(a.nbytes, 8)).upload(a).ptr
         d_vars, d_wit, d_sel, d_pub = up(circuit.wire_vars), up(circuit.witness), up(circuit.selector_evals), up(pub)
         return preprocess_dev(w, d_vars, n, circuit.num_vars, d_wit, d_sel, d_pub, circuit.public_inputs.shape[0], circuit.k, check)
-    finally:
-        for b in bufs:
-            b.free()

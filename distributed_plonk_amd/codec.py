@@ -19,6 +19,7 @@ import numpy as np
 
 from . import _ffi
 from .transcript import FQ_MODULI, serialize_g1
+from .worker import DeviceScope
 
 ENCODINGS = {"compressed": _ffi.PLONK_BYTES_COMPRESSED, "uncompressed": _ffi.PLONK_BYTES_UNCOMPRESSED}
 STATUS_BITS = {1: "no point has this x, or the pair is off the curve", 2: "point outside the r-subgroup", 8: "non-canonical encoding",
@@ -85,20 +86,8 @@ def fr_to_bytes_dev(w, d_fr: int, count: int, d_bytes: int, in_stride_u64: int =
 
 
 # ------------------------------------------------------------------------------------------------ host-array forms
-class _Bufs:
-    def __init__(self, w):
-        self.w, self.bufs = w, []
-
-    def __call__(self, nbytes: int):
-        self.bufs.append(self.w.alloc(max(nbytes, 8)))
-        return self.bufs[-1]
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        for b in self.bufs:
-            b.free()
+def _alloc(s: DeviceScope, nbytes: int):
+    return s.alloc(max(nbytes, 8))
 
 
 def g1_from_bytes(w, data, encoding: str = "compressed", check_subgroup: bool = True):
@@ -109,8 +98,8 @@ def g1_from_bytes(w, data, encoding: str = "compressed", check_subgroup: bool = 
     count = raw.size // nb
     if count == 0:
         return np.zeros((0, 2 * w.q64), np.uint64), np.zeros((0,), np.uint32)
-    with _Bufs(w) as alloc:
-        d_in, d_out, d_st = alloc(raw.nbytes).upload(raw), alloc(count * 16 * w.q64), alloc(count * 4)
+    with DeviceScope(w) as s:
+        d_in, d_out, d_st = _alloc(s, raw.nbytes).upload(raw), _alloc(s, count * 16 * w.q64), _alloc(s, count * 4)
         w.memset_dev(d_st.ptr, 0, count * 4)
         g1_from_bytes_dev(w, d_in.ptr, count, d_out.ptr, d_st.ptr, encoding, check_subgroup)
         return d_out.download((count, 2 * w.q64)), d_st.download((count,), dtype=np.uint32)
@@ -122,8 +111,8 @@ def g1_to_bytes(w, xy, encoding: str = "compressed") -> bytes:
     count, nb = xy.shape[0], g1_nbytes(w.curve_name, encoding)
     if count == 0:
         return b""
-    with _Bufs(w) as alloc:
-        d_in, d_out = alloc(xy.nbytes).upload(xy), alloc(count * nb)
+    with DeviceScope(w) as s:
+        d_in, d_out = _alloc(s, xy.nbytes).upload(xy), _alloc(s, count * nb)
         g1_to_bytes_dev(w, d_in.ptr, count, d_out.ptr, encoding)
         return d_out.download((count * nb,), dtype=np.uint8).tobytes()
 
@@ -136,8 +125,8 @@ def fr_from_bytes(w, data):
     count = raw.size // 32
     if count == 0:
         return np.zeros((0, 4), np.uint64), np.zeros((0,), np.uint32)
-    with _Bufs(w) as alloc:
-        d_in, d_out, d_st = alloc(raw.nbytes).upload(raw), alloc(count * 32), alloc(count * 4)
+    with DeviceScope(w) as s:
+        d_in, d_out, d_st = _alloc(s, raw.nbytes).upload(raw), _alloc(s, count * 32), _alloc(s, count * 4)
         w.memset_dev(d_st.ptr, 0, count * 4)
         fr_from_bytes_dev(w, d_in.ptr, count, d_out.ptr, d_st.ptr)
         return d_out.download((count, 4)), d_st.download((count,), dtype=np.uint32)
@@ -148,16 +137,16 @@ def fr_to_bytes(w, limbs) -> bytes:
     count = limbs.shape[0]
     if count == 0:
         return b""
-    with _Bufs(w) as alloc:
-        d_in, d_out = alloc(limbs.nbytes).upload(limbs), alloc(count * 32)
+    with DeviceScope(w) as s:
+        d_in, d_out = _alloc(s, limbs.nbytes).upload(limbs), _alloc(s, count * 32)
         fr_to_bytes_dev(w, d_in.ptr, count, d_out.ptr)
         return d_out.download((count * 32,), dtype=np.uint8).tobytes()
 
 
 # ------------------------------------------------------------------------------------------------ proofs and Vec<Commitment>
-def proofs_from_bytes_dev(w, blobs: Sequence[bytes]):
-    """Serialized proofs -> (DeviceBuffer of len(blobs) records of plonk_verify_batch_dev — the caller frees it —, status (K,) u32).  The
-    records stay on the device; only the status words come back.  ValueError for a blob of another length than proof_nbytes(curve)."""
+def _proofs_into(s: DeviceScope, blobs: Sequence[bytes]):
+    """proofs_from_bytes_dev with the records in a buffer of the scope `s`: what a caller that frees them with the rest of its call takes."""
+    w = s.worker
     nb = proof_nbytes(w.curve_name)
     blobs = [bytes(b) for b in blobs]
     for i, b in enumerate(blobs):
@@ -165,35 +154,34 @@ def proofs_from_bytes_dev(w, blobs: Sequence[bytes]):
             raise ValueError(f"proof {i}: {len(b)} bytes, a serialized proof on {w.curve_name} has {nb}")
     K = len(blobs)
     rec_u64 = 2 * w.q64 * NPTS + 4 * NEVALS
-    d_recs = w.alloc(max(K * rec_u64 * 8, 8))
+    d_recs = _alloc(s, K * rec_u64 * 8)
     if K == 0:
         return d_recs, np.zeros((0,), np.uint32)
-    d_in = d_st = None
-    try:
-        d_in = w.alloc(K * nb).upload(np.frombuffer(b"".join(blobs), dtype=np.uint8))
-        d_st = w.alloc(K * 4)
-        w.proofs_from_bytes_dev(d_in.ptr, K, d_recs.ptr, d_st.ptr)
-        status = d_st.download((K,), dtype=np.uint32)
-    except BaseException:
-        d_recs.free()
-        raise
-    finally:
-        for b in (d_in, d_st):
-            if b is not None:
-                b.free()
+    d_in = s.alloc(K * nb).upload(np.frombuffer(b"".join(blobs), dtype=np.uint8))
+    d_st = s.alloc(K * 4)
+    w.proofs_from_bytes_dev(d_in.ptr, K, d_recs.ptr, d_st.ptr)
+    status = d_st.download((K,), dtype=np.uint32)
+    s.free(d_in)
+    s.free(d_st)
     return d_recs, status
+
+
+def proofs_from_bytes_dev(w, blobs: Sequence[bytes]):
+    """Serialized proofs -> (DeviceBuffer of len(blobs) records of plonk_verify_batch_dev — the caller frees it —, status (K,) u32).  The
+    records stay on the device; only the status words come back.  ValueError for a blob of another length than proof_nbytes(curve)."""
+    with DeviceScope(w) as s:
+        d_recs, status = _proofs_into(s, blobs)
+        return s.release(d_recs), status
 
 
 def proof_from_bytes(w, blob: bytes) -> dict:
     """One serialized proof -> the dict `Prover.prove` returns (points as (xy, is_infinity), scalars as Montgomery limbs).  ValueError naming
     the status for a blob that does not decode."""
-    d_recs, status = proofs_from_bytes_dev(w, [blob])
-    try:
+    with DeviceScope(w) as s:
+        d_recs, status = _proofs_into(s, [blob])
         if status[0]:
             raise ValueError(f"proof_from_bytes: {status_text(status[0])}")
         rec = d_recs.download((2 * w.q64 * NPTS + 4 * NEVALS,))
-    finally:
-        d_recs.free()
     n2 = 2 * w.q64
     pt = lambda i: (rec[n2 * i:n2 * (i + 1)].copy(), not rec[n2 * i:n2 * (i + 1)].any())
     ev = lambda i: rec[n2 * NPTS + 4 * i:n2 * NPTS + 4 * (i + 1)].copy()

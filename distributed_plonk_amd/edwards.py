@@ -26,7 +26,7 @@ import numpy as np
 from . import fr as _fr
 from . import rescue as _rescue
 from .builder import BuiltCircuit, CircuitBuilder
-from .worker import PlonkWorker
+from .worker import DeviceScope, PlonkWorker
 
 NUM_PARAM_WORDS = 20                                  # a, d, G.x, G.y (4 limbs each, Montgomery), l (4 plain limbs)
 ON_CURVE, IN_SUBGROUP = 1, 2                          # bits of plonk_edwards_check_dev's flags
@@ -161,17 +161,11 @@ def check_dev(worker: PlonkWorker, params: EdwardsParams, d_points: int, count: 
 # ---------------------------------------------------------------------------------------------- host arrays in, host arrays out
 def _run(worker: PlonkWorker, arrays, out_shape, out_dtype, call):
     """upload `arrays`, call(pointers..., d_out), download d_out"""
-    bufs = []
-    try:
-        for a in arrays:
-            bufs.append(worker.alloc(a.nbytes).upload(a))
-        out = worker.alloc(int(np.prod(out_shape)) * np.dtype(out_dtype).itemsize)
-        bufs.append(out)
-        call(*[b.ptr for b in bufs])
+    with DeviceScope(worker) as s:
+        ptrs = [s.upload(a).ptr for a in arrays]
+        out = s.alloc(int(np.prod(out_shape)) * np.dtype(out_dtype).itemsize)
+        call(*ptrs, out.ptr)
         return out.download(out_shape, dtype=out_dtype)
-    finally:
-        for b in bufs:
-            b.free()
 
 
 def mul(worker: PlonkWorker, params: EdwardsParams, scalars, points) -> np.ndarray:
@@ -282,20 +276,13 @@ def schnorr_verify(worker: PlonkWorker, params: EdwardsParams, pks, messages, si
     pk, R = pk.copy(), R.copy()
     pk[~good], R[~good] = identity, identity
     c = challenge(worker, params, R, pk, m, rescue)
-    bufs = []
-    try:
-        for a in (s, c, pk, R):
-            bufs.append(worker.alloc(a.nbytes))
-            bufs[-1].upload(a)
-        bufs.append(worker.alloc(R.nbytes))
-        d_s, d_c, d_pk, d_R, d_lhs = bufs
+    with DeviceScope(worker) as scope:
+        d_s, d_c, d_pk, d_R = (scope.upload(a) for a in (s, c, pk, R))
+        d_lhs = scope.alloc(R.nbytes)
         fixed_mul_dev(worker, params, d_s.ptr, count, d_lhs.ptr)
         mul_dev(worker, params, d_c.ptr, d_pk.ptr, count, d_pk.ptr)
         add_dev(worker, params, d_R.ptr, d_pk.ptr, count, d_R.ptr)
         lhs, rhs = d_lhs.download(R.shape), d_R.download(R.shape)
-    finally:
-        for b in bufs:
-            b.free()
     return ok & (lhs == rhs).all(axis=(1, 2))
 
 

@@ -31,7 +31,7 @@ from . import edwards as _ed
 from . import rescue as _rescue
 from .builder import BuiltCircuit, CircuitBuilder
 from .edwards import EdwardsParams
-from .worker import PlonkWorker
+from .worker import DeviceScope, PlonkWorker
 
 keygen = _ed.fixed_mul                                # ek = [dk] G: (count, 4) -> (count, 2, 4)
 
@@ -98,18 +98,11 @@ def encrypt(worker: PlonkWorker, params: EdwardsParams, ek, msg, r, rescue=None)
         raise ValueError(f"r[{big[0]}] >= l: the randomness is a residue below the subgroup order")
     if count == 0:
         return ek.copy(), m.copy()
-    bufs = []
-    try:
-        for a in (ek, m, r):
-            bufs.append(worker.alloc(a.nbytes).upload(a))
-        bufs.append(worker.alloc(count * 64))
-        bufs.append(worker.alloc(count * 32))
-        d_ek, d_m, d_r, d_E, d_keys = bufs
+    with DeviceScope(worker) as s:
+        d_ek, d_m, d_r = (s.upload(a) for a in (ek, m, r))
+        d_E, d_keys = s.alloc(count * 64), s.alloc(count * 32)
         encrypt_dev(worker, params, d_ek.ptr, d_m.ptr, d_r.ptr, L, count, d_E.ptr, d_m.ptr, d_keys.ptr, rp)
         return d_E.download((count, 2, 4)), d_m.download(m.shape)
-    finally:
-        for b in bufs:
-            b.free()
 
 
 def decrypt(worker: PlonkWorker, params: EdwardsParams, dk, ciphertext, rescue=None):
@@ -123,19 +116,12 @@ def decrypt(worker: PlonkWorker, params: EdwardsParams, dk, ciphertext, rescue=N
     L = ct.shape[1]
     if count == 0:
         return ct.copy(), np.zeros(0, dtype=bool)
-    bufs = []
-    try:
-        for a in (dk, E, ct):
-            bufs.append(worker.alloc(a.nbytes).upload(a))
-        bufs.append(worker.alloc(count * 4))
-        bufs.append(worker.alloc(count * 32))
-        d_dk, d_E, d_ct, d_flags, d_keys = bufs
+    with DeviceScope(worker) as s:
+        d_dk, d_E, d_ct = (s.upload(a) for a in (dk, E, ct))
+        d_flags, d_keys = s.alloc(count * 4), s.alloc(count * 32)
         decrypt_dev(worker, params, d_dk.ptr, d_E.ptr, d_ct.ptr, L, count, d_ct.ptr, d_flags.ptr, d_keys.ptr, rp)
         flags = d_flags.download((count,), dtype=np.uint32)
         return d_ct.download(ct.shape), (flags & _ed.IN_SUBGROUP) != 0
-    finally:
-        for b in bufs:
-            b.free()
 
 
 # ---------------------------------------------------------------------------------------------- the circuit

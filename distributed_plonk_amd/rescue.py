@@ -52,7 +52,7 @@ from typing import Sequence
 import numpy as np
 
 from . import fr as _fr
-from .worker import PlonkWorker
+from .worker import DeviceScope, PlonkWorker, closing_on_error
 
 WIDTH, ROUNDS = 4, 12
 NUM_KEYS = 2 * ROUNDS + 1
@@ -121,13 +121,10 @@ def permute(worker: PlonkWorker, params: RescueParams, states) -> np.ndarray:
     s = np.ascontiguousarray(states, dtype=np.uint64).reshape(-1, WIDTH, 4)
     if s.shape[0] == 0:
         return s.copy()
-    buf = worker.alloc(s.nbytes)
-    try:
-        buf.upload(s)
+    with DeviceScope(worker) as scope:
+        buf = scope.upload(s)
         permute_dev(worker, params, buf.ptr, s.shape[0])
         return buf.download(s.shape)
-    finally:
-        buf.free()
 
 
 def merkle_dev(worker: PlonkWorker, params: RescueParams, d_nodes: int, log_leaves: int):
@@ -150,13 +147,11 @@ class MerkleTree:
         self.worker, self.params = worker, params
         self.num_leaves, self.log_leaves = L, L.bit_length() - 1
         self._nodes = None
-        self.d_nodes = worker.alloc((2 * L - 1) * 32)
-        try:
+        self._scope = DeviceScope(worker)
+        with closing_on_error(self._scope):
+            self.d_nodes = self._scope.alloc((2 * L - 1) * 32)
             worker.write_bytes(self.d_nodes.offset((L - 1) * 32), lv)
             merkle_dev(worker, params, self.d_nodes.ptr, self.log_leaves)
-        except BaseException:
-            self.d_nodes.free()
-            raise
 
     @property
     def nodes(self) -> np.ndarray:
@@ -184,8 +179,7 @@ class MerkleTree:
         return (np.stack(sibs) if sibs else np.zeros((0, 4), dtype=np.uint64)), bits
 
     def close(self):
-        if self.d_nodes.ptr:
-            self.d_nodes.free()
+        self._scope.close()
 
 
 # ---------------------------------------------------------------------------------------------- the ternary accumulator
@@ -237,18 +231,12 @@ class Accumulator:
         self.worker, self.params, self.height, self.count = worker, params, height, el.shape[0]
         self.num_nodes = sum(self.level_counts)
         self._nodes = None
-        self.d_elems = worker.alloc(el.nbytes)
-        try:
-            self.d_nodes = worker.alloc(self.num_nodes * 32)
-        except BaseException:
-            self.d_elems.free()
-            raise
-        try:
+        self._scope = DeviceScope(worker)
+        with closing_on_error(self._scope):
+            self.d_elems = self._scope.alloc(el.nbytes)
+            self.d_nodes = self._scope.alloc(self.num_nodes * 32)
             self.d_elems.upload(el)
             acc_build_dev(worker, params, self.d_elems.ptr, self.count, height, self.d_nodes.ptr)
-        except BaseException:
-            self.close()
-            raise
 
     @property
     def nodes(self) -> np.ndarray:
@@ -284,25 +272,16 @@ class Accumulator:
         membership.membership_circuit(curve, height, len(uids)).  Gathered on the device from d_nodes and d_elems; only the uids go up."""
         u = np.ascontiguousarray(uids, dtype=np.uint64).reshape(-1)
         m = u.shape[0]
-        out = self.worker.alloc(max(1, (2 + 4 * self.height) * m) * 32)
-        d_uids = None
-        try:
-            d_uids = self.worker.alloc(max(1, m) * 8)
+        with DeviceScope(self.worker) as s:
+            out = s.alloc(max(1, (2 + 4 * self.height) * m) * 32)
+            d_uids = s.alloc(max(1, m) * 8)
             if m:
                 d_uids.upload(u)
             acc_paths_dev(self.worker, self.d_nodes.ptr, self.count, self.height, self.d_elems.ptr, d_uids.ptr, m, out.ptr)
-        except BaseException:
-            out.free()
-            raise
-        finally:
-            if d_uids is not None:
-                d_uids.free()
-        return out
+            return s.release(out)
 
     def close(self):
-        for b in (self.d_nodes, self.d_elems):
-            if b.ptr:
-                b.free()
+        self._scope.close()
 
 
 # ---------------------------------------------------------------------------------------------- the sponge and the counter-mode stream
@@ -337,17 +316,11 @@ def sponge(worker: PlonkWorker, params: RescueParams, inputs, n_out: int = 1) ->
         raise ValueError(f"sponge: n_out = {n_out!r} (1, 2 or 3)")
     if count == 0:
         return np.zeros((0, n_out, 4), dtype=np.uint64)
-    d_in = worker.alloc(x.nbytes)
-    d_out = None
-    try:
-        d_out = worker.alloc(count * n_out * 32)
+    with DeviceScope(worker) as s:
+        d_in, d_out = s.alloc(x.nbytes), s.alloc(count * n_out * 32)
         d_in.upload(x)
         sponge_dev(worker, params, d_in.ptr, L, count, n_out, d_out.ptr)
         return d_out.download((count, n_out, 4))
-    finally:
-        d_in.free()
-        if d_out is not None:
-            d_out.free()
 
 
 def stream_dev(worker: PlonkWorker, params: RescueParams, d_keys: int, d_in: int, L: int, count: int, d_out: int, decrypt: bool = False):
@@ -371,15 +344,9 @@ def stream(worker: PlonkWorker, params: RescueParams, keys, texts, decrypt: bool
     _text_shape(L, "stream")
     if count == 0:
         return x.copy()
-    d_k = worker.alloc(k.nbytes)
-    d_x = None
-    try:
-        d_x = worker.alloc(x.nbytes)
+    with DeviceScope(worker) as s:
+        d_k, d_x = s.alloc(k.nbytes), s.alloc(x.nbytes)
         d_k.upload(k)
         d_x.upload(x)
         stream_dev(worker, params, d_k.ptr, d_x.ptr, L, count, d_x.ptr, decrypt)
         return d_x.download(x.shape)
-    finally:
-        d_k.free()
-        if d_x is not None:
-            d_x.free()

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 
 from . import fr as _fr
-from .worker import PlonkWorker
+from .worker import DeviceScope, PlonkWorker, closing_on_error
 
 NUM_WIRE_TYPES = 5
 NUM_SELECTORS = 13
@@ -39,45 +39,41 @@ class SyntheticInstance:
         n = self.n = 1 << log_n
         self.log_n, self.num_inputs, self.tau = log_n, num_inputs, tau
         self.k = wire_subset_separators(f, seed)
-        self._bufs = []
-        alloc = lambda n_fr: self._keep(w.alloc(max(n_fr, 1) * 32))
-        self.d_wires = alloc(5 * n)
-        d_sel_ev = alloc(NUM_SELECTORS * n)
-        d_sig_ev = alloc(NUM_WIRE_TYPES * n)
-        self.d_id = alloc(5 * n)
-        self.d_idx = self._keep(w.alloc(5 * n * 8))
-        self.d_pi = alloc(n)
-        w.synth_circuit(seed, n, num_inputs, self.k, self.d_wires.ptr, d_sel_ev.ptr, d_sig_ev.ptr, self.d_id.ptr, self.d_idx.ptr, self.d_pi.ptr)
-        self.d_sel_ev, self.d_sig_ev = d_sel_ev, d_sig_ev
-        # proving key: selector and sigma polynomials in coefficient form (n-point iNTTs; d_in is consumed, so transform a copy)
-        self.d_sel = alloc(NUM_SELECTORS * n)
-        self.d_sig = alloc(NUM_WIRE_TYPES * n)
-        tmp = w.alloc(n * 32)
-        try:
+        self._scope = DeviceScope(w)
+        with closing_on_error(self._scope):
+            alloc = lambda n_fr: self._scope.alloc(max(n_fr, 1) * 32)
+            self.d_wires = alloc(5 * n)
+            d_sel_ev = alloc(NUM_SELECTORS * n)
+            d_sig_ev = alloc(NUM_WIRE_TYPES * n)
+            self.d_id = alloc(5 * n)
+            self.d_idx = self._scope.alloc(5 * n * 8)
+            self.d_pi = alloc(n)
+            w.synth_circuit(seed, n, num_inputs, self.k, self.d_wires.ptr, d_sel_ev.ptr, d_sig_ev.ptr, self.d_id.ptr, self.d_idx.ptr, self.d_pi.ptr)
+            self.d_sel_ev, self.d_sig_ev = d_sel_ev, d_sig_ev
+            # proving key: selector and sigma polynomials in coefficient form (n-point iNTTs; d_in is consumed, so transform a copy).  The loop of
+            # circuit._proving_key_polys, kept here because circuit.py imports this module
+            self.d_sel = alloc(NUM_SELECTORS * n)
+            self.d_sig = alloc(NUM_WIRE_TYPES * n)
+            tmp = self._scope.alloc(n * 32)
             for src, dst, cnt in ((d_sel_ev, self.d_sel, NUM_SELECTORS), (d_sig_ev, self.d_sig, NUM_WIRE_TYPES)):
                 for t in range(cnt):
                     w.memcpy_d2d(tmp.ptr, src.ptr + t * n * 32, n * 32)
                     w.ntt_dev(tmp.ptr, dst.ptr + t * n * 32, n, True, False)
-        finally:
-            tmp.free()
-        self.wev = [self.d_wires.ptr + i * n * 32 for i in range(5)]
-        self.sel_ptrs = [self.d_sel.ptr + t * n * 32 for t in range(NUM_SELECTORS)]
-        self.sig_ptrs = [self.d_sig.ptr + t * n * 32 for t in range(NUM_WIRE_TYPES)]
-        self.key_size = ((n + 3 + 31) >> 5) << 5
-        self.d_ck = None
-        if tau is not None:
-            q = 64 if w.curve_name == "bn254" else 96
-            self.d_ck = self._keep(w.alloc(self.key_size * q))
-            w.memset_dev(self.d_ck.ptr, 0, self.key_size * q)                 # x = y = 0: the padding points at infinity
-            w.synth_srs(f.to_limbs(tau), n + 3, self.d_ck.ptr)
-            if init_worker:
-                for ctx in (w, *helpers):
-                    ctx.init_dev(self.d_ck.ptr, self.key_size, n, 8 * n)
-        w.sync()
-
-    def _keep(self, b):
-        self._bufs.append(b)
-        return b
+            self._scope.free(tmp)
+            self.wev = [self.d_wires.ptr + i * n * 32 for i in range(5)]
+            self.sel_ptrs = [self.d_sel.ptr + t * n * 32 for t in range(NUM_SELECTORS)]
+            self.sig_ptrs = [self.d_sig.ptr + t * n * 32 for t in range(NUM_WIRE_TYPES)]
+            self.key_size = ((n + 3 + 31) >> 5) << 5
+            self.d_ck = None
+            if tau is not None:
+                q = 64 if w.curve_name == "bn254" else 96
+                self.d_ck = self._scope.alloc(self.key_size * q)
+                w.memset_dev(self.d_ck.ptr, 0, self.key_size * q)                 # x = y = 0: the padding points at infinity
+                w.synth_srs(f.to_limbs(tau), n + 3, self.d_ck.ptr)
+                if init_worker:
+                    for ctx in (w, *helpers):
+                        ctx.init_dev(self.d_ck.ptr, self.key_size, n, 8 * n)
+            w.sync()
 
     def public_inputs(self) -> np.ndarray:
         """`circuit.public_input()`: the num_inputs values (not padded) -> (num_inputs, 4)."""
@@ -92,6 +88,4 @@ class SyntheticInstance:
                     selector_evals=self.d_sel_ev.download((NUM_SELECTORS, n, 4)), sigma_evals=self.d_sig_ev.download((NUM_WIRE_TYPES, n, 4)))
 
     def close(self):
-        for b in self._bufs:
-            b.free()
-        self._bufs = []
+        self._scope.close()

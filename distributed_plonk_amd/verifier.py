@@ -30,6 +30,7 @@ import numpy as np
 from . import _ffi
 from . import fr as _fr
 from .transcript import FQ_MODULI, PlonkTranscript
+from .worker import DeviceScope, closing_on_error
 
 NPTS, NEVALS = 13, 10
 STATUS_BITS = {1: "point off the curve", 2: "point outside the r-subgroup", 4: "zeta in the evaluation domain", 8: "non-canonical encoding"}
@@ -143,27 +144,13 @@ class OpenKey:
         return cls(curve, xy, pts[0], pts[1])
 
 
-class _Buffers(list):
-    """The device buffers of one call: `with _Buffers(worker) as bufs` frees every one of them on every exit, exceptions included."""
+def _alloc(bufs: DeviceScope, nbytes: int):
+    return bufs.alloc(max(nbytes, 8))
 
-    def __init__(self, worker):
-        super().__init__()
-        self.worker = worker
 
-    def alloc(self, nbytes: int):
-        self.append(self.worker.alloc(max(nbytes, 8)))
-        return self[-1]
-
-    def upload(self, arr: np.ndarray) -> int:
-        """The array in a buffer of its own: the device pointer, 0 for an empty array (nothing is allocated for one)."""
-        return self.alloc(arr.nbytes).upload(arr).ptr if arr.nbytes else 0
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        for b in self:
-            b.free()
+def _upload(bufs: DeviceScope, arr: np.ndarray) -> int:
+    """The array in a buffer of its own: the device pointer, 0 for an empty array (nothing is allocated for one)."""
+    return _alloc(bufs, arr.nbytes).upload(arr).ptr if arr.nbytes else 0
 
 
 def _vk_state(curve: str, vk: dict, num_inputs: int) -> _ffi.VerifyKey:
@@ -196,7 +183,7 @@ def device_verify(worker, vk: dict, public_inputs_list, proofs, rho: np.ndarray,
     """The device part for K proofs: (points [K, 2 (rho B, rho A), 2Q] u64, status [K] u32, debug [K, 9, 4] or None)."""
     K = len(proofs)
     pis, num_inputs = _one_key_inputs(K, public_inputs_list, rho)
-    with _Buffers(worker) as bufs:
+    with DeviceScope(worker) as bufs:
         d_recs, d_pub = _upload_batch(bufs, proofs, pis)
         return device_verify_records(worker, vk, num_inputs, K, d_recs, d_pub, rho, debug)
 
@@ -204,7 +191,7 @@ def device_verify(worker, vk: dict, public_inputs_list, proofs, rho: np.ndarray,
 def device_verify_records(worker, vk: dict, num_inputs: int, K: int, d_recs: int, d_pub: int, rho: np.ndarray, debug: bool = False):
     """What device_verify does after the upload: K proof records and K x num_inputs public inputs already on the device (pointers) ->
     (points, status, debug) as device_verify returns them."""
-    with _Buffers(worker) as bufs:
+    with DeviceScope(worker) as bufs:
         return _download_pairs(K, *_launch_pairs(bufs, K, rho, debug, _one_key_launch(bufs, vk, num_inputs, K, d_recs, d_pub)))
 
 
@@ -220,29 +207,28 @@ def _one_key_inputs(K: int, public_inputs_list, rho: np.ndarray):
     return pis, num_inputs
 
 
-def _upload_batch(bufs: _Buffers, proofs, pis, *more):
+def _upload_batch(bufs: DeviceScope, proofs, pis, *more):
     """A batch of proof dicts on the device: the pointers of the records, of the concatenated public inputs and of every array of `more`
     (key indices, offsets), 0 for an empty array."""
     curve = bufs.worker.curve_name
     recs = np.stack([proof_record(curve, p) for p in proofs]) if len(proofs) else np.zeros((0, 2 * _q64(curve) * NPTS + 4 * NEVALS), np.uint64)
-    return [bufs.upload(arr) for arr in (recs, np.concatenate(pis + [np.zeros((0, 4), np.uint64)]), *more)]
+    return [_upload(bufs, arr) for arr in (recs, np.concatenate(pis + [np.zeros((0, 4), np.uint64)]), *more)]
 
 
-def _decode_batch(bufs: _Buffers, public_inputs_bytes: Sequence[bytes], proof_blobs):
-    """A batch as provers send it, decoded on the device: the proofs by codec.proofs_from_bytes_dev, all public inputs (32 bytes each, any
-    number per proof) by ONE plonk_fr_from_bytes_dev launch over their concatenation.  (d_recs, d_pub or 0, the K + 1 offsets of the proofs'
+def _decode_batch(bufs: DeviceScope, public_inputs_bytes: Sequence[bytes], proof_blobs):
+    """A batch as provers send it, decoded on the device: the proofs as codec.proofs_from_bytes_dev does, their records in a buffer of
+    `bufs`, all public inputs (32 bytes each, any number per proof) by ONE plonk_fr_from_bytes_dev launch over their concatenation.  (d_recs, d_pub or 0, the K + 1 offsets of the proofs'
     spans in d_pub, decode [K] u32): decode[j] ORs the codec's status words of proof j and of its inputs."""
     from . import codec
     worker, K = bufs.worker, len(proof_blobs)
-    d_recs, decode = codec.proofs_from_bytes_dev(worker, proof_blobs)
-    bufs.append(d_recs)
+    d_recs, decode = codec._proofs_into(bufs, proof_blobs)
     off = np.concatenate([[0], np.cumsum([len(p) // 32 for p in public_inputs_bytes])]).astype(np.uint64)
     total = int(off[-1])
     d_pub = 0
     if total:
-        d_raw = bufs.upload(np.frombuffer(b"".join(public_inputs_bytes), dtype=np.uint8))
-        d_pub = bufs.alloc(total * 32).ptr
-        d_st = bufs.alloc(total * 4)
+        d_raw = _upload(bufs, np.frombuffer(b"".join(public_inputs_bytes), dtype=np.uint8))
+        d_pub = _alloc(bufs, total * 32).ptr
+        d_st = _alloc(bufs, total * 4)
         worker.memset_dev(d_st.ptr, 0, total * 4)
         worker.fr_from_bytes_dev(d_raw, 32, total, d_pub, 4, d_st.ptr, 1)
         st = d_st.download((total,), dtype=np.uint32)
@@ -250,13 +236,13 @@ def _decode_batch(bufs: _Buffers, public_inputs_bytes: Sequence[bytes], proof_bl
     return d_recs.ptr, d_pub, off, np.ascontiguousarray(decode, dtype=np.uint32)
 
 
-def _one_key_launch(bufs: _Buffers, vk: dict, num_inputs: int, K: int, d_recs: int, d_pub: int):
+def _one_key_launch(bufs: DeviceScope, vk: dict, num_inputs: int, K: int, d_recs: int, d_pub: int):
     """The launch of `plonk_verify_batch_dev` under vk for _launch_pairs, the key's 18 commitments uploaded.  A key of the wrong shape raises."""
     curve = bufs.worker.curve_name
     if len(vk["selector_comms"]) != 13 or len(vk["sigma_comms"]) != 5:
         raise ValueError("verifying key shape")
     key = _vk_state(curve, vk, num_inputs)
-    key.d_comms = bufs.upload(np.concatenate([_point_xy(curve, c) for c in list(vk["selector_comms"]) + list(vk["sigma_comms"])]))
+    key.d_comms = _upload(bufs, np.concatenate([_point_xy(curve, c) for c in list(vk["selector_comms"]) + list(vk["sigma_comms"])]))
     return lambda *outputs: bufs.worker.verify_batch_dev(key, K, d_recs, d_pub if num_inputs else 0, *outputs)
 
 
@@ -265,14 +251,14 @@ def _multi_launch(worker, keys: "VerifyKeySet", K: int, d_recs: int, d_idx: int,
     return lambda *outputs: worker.verify_batch_multi_dev(keys.keys, keys.n_vks, K, d_recs, d_idx, d_pub if pub_total else 0, d_off, pub_total, *outputs)
 
 
-def _launch_pairs(bufs: _Buffers, K: int, rho: np.ndarray, debug: bool, launch):
+def _launch_pairs(bufs: DeviceScope, K: int, rho: np.ndarray, debug: bool, launch):
     """The per-proof kernels, enqueued: rho uploaded, the buffers of the K output pairs [rho B, rho A], the K status words and (debug) the
     K x 9 intermediate scalars allocated, and launch(d_rho, d_out, d_status, d_debug or 0) called on their pointers.  (d_out, d_status,
     d_debug or None): DeviceBuffers that bufs owns."""
-    d_rho = bufs.upload(np.ascontiguousarray(rho, dtype=np.uint64))
-    d_out = bufs.alloc(K * 2 * 2 * _q64(bufs.worker.curve_name) * 8)
-    d_status = bufs.alloc(K * 4)
-    d_dbg = bufs.alloc(K * 9 * 32) if debug else None
+    d_rho = _upload(bufs, np.ascontiguousarray(rho, dtype=np.uint64))
+    d_out = _alloc(bufs, K * 2 * 2 * _q64(bufs.worker.curve_name) * 8)
+    d_status = _alloc(bufs, K * 4)
+    d_dbg = _alloc(bufs, K * 9 * 32) if debug else None
     if debug:
         bufs.worker.memset_dev(d_dbg.ptr, 0, K * 9 * 32)
     launch(d_rho, d_out.ptr, d_status.ptr, d_dbg.ptr if debug else 0)
@@ -297,12 +283,10 @@ def check_srs(worker, open_key: OpenKey, count: int, seed: Optional[int] = None)
     f = _fr.FIELDS[curve]
     draw = (lambda: secrets.randbelow(f.p - 1) + 1) if seed is None else (lambda r=random.Random(seed): r.randrange(1, f.p))
     rho = np.array([[(x >> (64 * j)) & (2 ** 64 - 1) for j in range(4)] for x in (draw() for _ in range(count))], dtype=np.uint64)   # canonical
-    d = worker.alloc(max(rho.nbytes, 8)).upload(rho)
-    try:
+    with DeviceScope(worker) as bufs:
+        d = _alloc(bufs, rho.nbytes).upload(rho)
         s0, inf0 = worker.g1_to_affine(worker.msm_dev(0, count, d.ptr))
         s1, inf1 = worker.g1_to_affine(worker.msm_dev(1, count + 1, d.ptr))
-    finally:
-        d.free()
     if inf0 or inf1:
         return False
     s0 = s0.reshape(-1)
@@ -345,16 +329,16 @@ class VerifyKeySet:
         self.num_inputs = counts
         self.domain_sizes = [int(vk["domain_size"]) for vk in vks]
         self.keys = (_ffi.VerifyKey * len(vks))()
-        self._comms = worker.alloc(len(vks) * 18 * 2 * n64 * 8).upload(np.concatenate(comms))
-        for i, vk in enumerate(vks):
-            key = _vk_state(curve, vk, counts[i])
-            key.d_comms = self._comms.ptr + i * 18 * 2 * n64 * 8
-            self.keys[i] = key
+        self._scope = DeviceScope(worker)
+        with closing_on_error(self._scope):
+            d_comms = self._scope.alloc(len(vks) * 18 * 2 * n64 * 8).upload(np.concatenate(comms))
+            for i, vk in enumerate(vks):
+                key = _vk_state(curve, vk, counts[i])
+                key.d_comms = d_comms.ptr + i * 18 * 2 * n64 * 8
+                self.keys[i] = key
 
     def close(self):
-        if self._comms is not None:
-            self._comms.free()
-            self._comms = None
+        self._scope.close()
 
     def __enter__(self):
         return self
@@ -387,12 +371,12 @@ def device_verify_multi(worker, keys: VerifyKeySet, vk_index, public_inputs_list
     if len(public_inputs_list) != K or len(vk_index) != K or rho.shape[0] != K:
         raise ValueError("one key index, one public-input list and one rho per proof")
     pis = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 4) for p in public_inputs_list]
-    with _Buffers(worker) as bufs:
+    with DeviceScope(worker) as bufs:
         launch = _multi_launch(worker, keys, K, *_upload_multi(bufs, vk_index, pis, proofs, _offsets))
         return _download_pairs(K, *_launch_pairs(bufs, K, rho, debug, launch))
 
 
-def _upload_multi(bufs: _Buffers, vk_index, pis, proofs, offsets=None):
+def _upload_multi(bufs: DeviceScope, vk_index, pis, proofs, offsets=None):
     """_upload_batch with the key indices and the K + 1 offsets of the ragged public-input list: (d_recs, d_idx, d_pub, d_off, pub_total)."""
     off = np.concatenate([[0], np.cumsum([p.shape[0] for p in pis])]).astype(np.uint64) if offsets is None else np.asarray(offsets, dtype=np.uint64)
     if off.shape != (len(proofs) + 1,):
@@ -415,10 +399,10 @@ def g1_sum_tree(worker, points: np.ndarray, mask: Optional[np.ndarray] = None) -
     if K == 0:
         worker.g1_sum_tree_dev(0, 0, 0, 0)
         return np.zeros((0, 2, 2 * n64), np.uint64)
-    with _Buffers(worker) as bufs:
-        d_mask = bufs.upload(np.ascontiguousarray(mask, dtype=np.uint32).reshape(K)) if mask is not None else 0
-        d_tree = bufs.alloc((2 * tree_leaves(K) - 1) * 4 * n64 * 8)
-        worker.g1_sum_tree_dev(bufs.upload(points), K, d_mask, d_tree.ptr)
+    with DeviceScope(worker) as bufs:
+        d_mask = _upload(bufs, np.ascontiguousarray(mask, dtype=np.uint32).reshape(K)) if mask is not None else 0
+        d_tree = _alloc(bufs, (2 * tree_leaves(K) - 1) * 4 * n64 * 8)
+        worker.g1_sum_tree_dev(_upload(bufs, points), K, d_mask, d_tree.ptr)
         return d_tree.download((2 * tree_leaves(K) - 1, 2, 2 * n64))
 
 
@@ -475,7 +459,7 @@ def _bisect_on_device_tree(worker, open_key: OpenKey, d_tree, K: int, live: Sequ
     return bisect_tree(tree_leaves(K), live, holds)
 
 
-def _fold(bufs: _Buffers, open_key: OpenKey, K: int, rho: np.ndarray, launch, decode: Optional[np.ndarray], stats: Optional[dict]) -> list:
+def _fold(bufs: DeviceScope, open_key: OpenKey, K: int, rho: np.ndarray, launch, decode: Optional[np.ndarray], stats: Optional[dict]) -> list:
     """The fold of every batch function, and the one place that fills `stats`: the per-proof pairs (_launch_pairs), the sum tree over
     them (`plonk_g1_sum_tree_dev`) masked by the status words — ORed with the decode words of the bytes route, where a proof that did not
     decode has to stay out of every sum —, and the bisection over its nodes.  Only status words and tree nodes are read back, never the K
@@ -492,8 +476,8 @@ def _fold(bufs: _Buffers, open_key: OpenKey, K: int, rho: np.ndarray, launch, de
         if decode is not None:
             status = d_status.download((K,), dtype=np.uint32)
             mask = status | decode
-            d_mask = bufs.alloc(K * 4).upload(mask)
-        d_tree = bufs.alloc((2 * tree_leaves(K) - 1) * 2 * 2 * _q64(worker.curve_name) * 8)
+            d_mask = _alloc(bufs, K * 4).upload(mask)
+        d_tree = _alloc(bufs, (2 * tree_leaves(K) - 1) * 2 * 2 * _q64(worker.curve_name) * 8)
         worker.g1_sum_tree_dev(d_out.ptr, K, d_mask.ptr, d_tree.ptr)
         if kms is not None:
             kms["tree"] = worker.last_kernel_ms()
@@ -524,7 +508,7 @@ def batch_verify(worker, vk: dict, open_key: OpenKey, public_inputs_list, proofs
     K = len(proofs)
     rho = _rhos(curve, K, seed) if _rho is None else _rho
     pis, num_inputs = _one_key_inputs(K, public_inputs_list, rho)
-    with _Buffers(worker) as bufs:
+    with DeviceScope(worker) as bufs:
         d_recs, d_pub = _upload_batch(bufs, proofs, pis)
         return _fold(bufs, open_key, K, rho, _one_key_launch(bufs, vk, num_inputs, K, d_recs, d_pub), None, stats)
 
@@ -543,7 +527,7 @@ def batch_verify_bytes(worker, vk: dict, open_key: OpenKey, public_inputs_bytes,
     if any(len(p) % 32 or len(p) != len(pubs[0]) for p in pubs):
         raise ValueError("every proof of a batch needs the same number of public inputs, 32 bytes each")
     num_inputs = len(pubs[0]) // 32 if K else 0
-    with _Buffers(worker) as bufs:
+    with DeviceScope(worker) as bufs:
         d_recs, d_pub, _, decode = _decode_batch(bufs, pubs, proof_blobs)
         launch = _one_key_launch(bufs, vk, num_inputs, K, d_recs, d_pub) if K else None     # an empty batch does not look at the key
         return _fold(bufs, open_key, K, _rhos(curve, K, seed), launch, decode, stats)
@@ -567,7 +551,7 @@ def batch_verify_multi(worker, keys, open_key: OpenKey, vk_index, public_inputs_
     pis = [np.ascontiguousarray(p, dtype=np.uint64).reshape(-1, 4) for p in public_inputs_list]
     keyset, owned = _key_set(worker, keys, vk_index, pis)
     try:
-        with _Buffers(worker) as bufs:
+        with DeviceScope(worker) as bufs:
             rho = _rhos(curve, K, seed) if _rho is None else _rho
             return _fold(bufs, open_key, K, rho, _multi_launch(worker, keyset, K, *_upload_multi(bufs, vk_index, pis, proofs)), None, stats)
     finally:
@@ -590,9 +574,9 @@ def batch_verify_multi_bytes(worker, keys, open_key: OpenKey, vk_index, public_i
         raise ValueError("public inputs are 32 bytes each")
     keyset, owned = _key_set(worker, keys, vk_index, [np.zeros((len(p) // 32, 4), np.uint64) for p in pubs])
     try:
-        with _Buffers(worker) as bufs:
+        with DeviceScope(worker) as bufs:
             d_recs, d_pub, off, decode = _decode_batch(bufs, pubs, proof_blobs)
-            d_idx, d_off = bufs.upload(np.asarray(vk_index, dtype=np.uint32)), bufs.upload(off)
+            d_idx, d_off = _upload(bufs, np.asarray(vk_index, dtype=np.uint32)), _upload(bufs, off)
             launch = _multi_launch(worker, keyset, K, d_recs, d_idx, d_pub, d_off, int(off[-1]))
             return _fold(bufs, open_key, K, _rhos(curve, K, seed), launch, decode, stats)
     finally:

@@ -6,6 +6,7 @@ libplonk_hip.so on one MI355X.  numpy arrays are uint64 limbs in the reference's
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Callable, Optional, Sequence
 
@@ -56,6 +57,60 @@ class DeviceBuffer:
 
     def __cuda_array_interface_for__(self, nbytes=None):
         return {"shape": ((nbytes or self.nbytes) // 8,), "typestr": "<i8", "data": (self.ptr, False), "version": 2}
+
+
+class DeviceScope:
+    """The owner of the DeviceBuffers made through it: `with worker.scope() as s:` frees them on every exit of a call, and an object that holds
+    buffers for its lifetime keeps a scope and closes it in its close().  A buffer leaves by release() (the caller owns it from then on) or by
+    free().  Freeing is DeviceBuffer.free(), which synchronises the context's stream first: safe after a launch that a later step's failure
+    left enqueued."""
+
+    def __init__(self, worker: "PlonkWorker"):
+        self.worker, self._bufs = worker, []
+
+    def alloc(self, nbytes: int) -> DeviceBuffer:
+        self._bufs.append(self.worker.alloc(nbytes))
+        return self._bufs[-1]
+
+    def upload(self, arr: np.ndarray) -> DeviceBuffer:
+        """The array in a buffer of its size, registered before the copy: one whose upload raises is still freed."""
+        arr = np.ascontiguousarray(arr)
+        return self.alloc(arr.nbytes).upload(arr)
+
+    def release(self, buf: DeviceBuffer) -> DeviceBuffer:
+        self._bufs.remove(buf)
+        return buf
+
+    def free(self, buf: DeviceBuffer):
+        self.release(buf).free()
+
+    def close(self):
+        """Free every buffer still registered, each of them even when a free raises; the first such error is raised at the end."""
+        bufs, self._bufs, first = self._bufs, [], None
+        for b in bufs:
+            try:
+                b.free()
+            except BaseException as e:  # noqa: BLE001 - re-raised below, after the others were freed
+                first = first or e
+        if first is not None:
+            raise first
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+@contextlib.contextmanager
+def closing_on_error(owner):
+    """`with closing_on_error(x):` calls x.close() when the block raises and leaves x open when it does not: for the constructor of an object that
+    keeps a scope, and for a function that fills such an object before it returns it."""
+    try:
+        yield owner
+    except BaseException:
+        owner.close()
+        raise
 
 
 class PlonkWorker:
@@ -361,6 +416,9 @@ class PlonkWorker:
 
     def alloc(self, nbytes: int) -> DeviceBuffer:
         return DeviceBuffer(self, nbytes)
+
+    def scope(self) -> DeviceScope:
+        return DeviceScope(self)
 
     def read_bytes(self, src: int, nbytes: int) -> np.ndarray:
         """device -> a fresh host array of int64 words (host-staged transports)."""
