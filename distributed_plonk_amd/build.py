@@ -16,7 +16,7 @@ LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(HERE, "lib", "obj")
 OUT = os.path.join(LIBDIR, "libplonk_hip.so")
 UNITS = ["plonk_api.hip", "ntt_engine.hip", "msm_engine.hip", "synth.hip", "quotient.hip", "poly_ops.hip", "comm_rccl.hip"]
-HEADERS = ["fp.hpp", "fp29.hpp", "flimb.hpp", "ec.hpp", "ec_lazy.hpp", "constants.h", "ntt_kernels.hpp", "msm_kernels.hpp", "plonk_internal.hpp", "circuit_kernels.hpp", "solve_kernels.hpp", "solve_hints.hpp", "rescue_kernels.hpp", "rescue_acc_kernels.hpp", "edwards_kernels.hpp", "elgamal_kernels.hpp", "pairing.hpp", "verify_kernels.hpp", "codec_kernels.hpp",
+HEADERS = ["fp.hpp", "fp29.hpp", "flimb.hpp", "ec.hpp", "ec_lazy.hpp", "constants.h", "ntt_kernels.hpp", "msm_kernels.hpp", "plonk_internal.hpp", "circuit_kernels.hpp", "solve_kernels.hpp", "solve_hints.hpp", "rescue_kernels.hpp", "rescue_acc_kernels.hpp", "edwards_kernels.hpp", "elgamal_kernels.hpp", "pairing.hpp", "verify_kernels.hpp", "codec_kernels.hpp", "kzg_kernels.hpp",
            "../../include/plonk_hip.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",

@@ -1082,6 +1082,39 @@ extern "C" int plonk_poly_div_linear_dev(plonk_ctx* ctx, const void* d_poly, siz
     if (rc) return rc;
     return poly_div_linear_run(ctx->tables, d_poly, len, point, d_out, ctx->d_scratch2, ctx->stream);
 }
+// Openings of one polynomial at many device-resident points (csrc/kzg_kernels.hpp): nothing per point happens on the host.
+static bool spans_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return na && nb && x < y + nb && y < x + na;
+}
+extern "C" size_t plonk_poly_open_many_tile(void) { return poly_open_many_tile(); }
+extern "C" size_t plonk_poly_open_many_top_lanes(void) { return poly_open_many_top_lanes(); }
+extern "C" int plonk_poly_open_many_dev(plonk_ctx* ctx, const void* d_poly, size_t len, const void* d_points, size_t m, void* d_values, void* d_quotients,
+                                        size_t q_stride, void* d_status) {
+    const char* who = "plonk_poly_open_many_dev";
+    CHECK_CTX(ctx);
+    if (len >= ((size_t)1 << 30)) return plonk_fail(PLONK_ERR_ARG, "%s: %zu coefficients (limit 2^30)", who, len);
+    if (m > ((size_t)1 << 16)) return plonk_fail(PLONK_ERR_ARG, "%s: %zu points (at most 2^16 per call)", who, m);
+    if (m == 0) return PLONK_OK;
+    if ((!d_poly && len) || !d_points || !d_values || !d_status) return plonk_fail(PLONK_ERR_ARG, "%s: null", who);
+    const size_t row = len > 1 ? len - 1 : 0;
+    if (d_quotients && q_stride < row) return plonk_fail(PLONK_ERR_ARG, "%s: q_stride %zu below len - 1 = %zu", who, q_stride, row);
+    const size_t q_bytes = d_quotients && row ? ((m - 1) * q_stride + row) * 32 : 0;
+    const struct { const void* p; size_t n; const char* name; } outs[3] = {{d_values, m * 32, "d_values"}, {d_quotients, q_bytes, "d_quotients"}, {d_status, m * 4, "d_status"}};
+    for (int i = 0; i < 3; i++) {
+        if (spans_overlap(outs[i].p, outs[i].n, d_poly, len * 32)) return plonk_fail(PLONK_ERR_ARG, "%s: %s overlaps d_poly", who, outs[i].name);
+        if (spans_overlap(outs[i].p, outs[i].n, d_points, m * 32)) return plonk_fail(PLONK_ERR_ARG, "%s: %s overlaps d_points", who, outs[i].name);
+        for (int k = i + 1; k < 3; k++)
+            if (spans_overlap(outs[i].p, outs[i].n, outs[k].p, outs[k].n)) return plonk_fail(PLONK_ERR_ARG, "%s: %s overlaps %s", who, outs[i].name, outs[k].name);
+    }
+    int rc = ensure_scratch2(ctx, poly_open_many_scratch_bytes(len, m));
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    rc = poly_open_many_run(ctx->tables, d_poly, len, d_points, m, d_values, d_quotients, q_stride, d_status, ctx->d_scratch2, ctx->stream);
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    ctx->ev_valid = true;
+    return rc;
+}
 extern "C" int plonk_poly_degree_dev(plonk_ctx* ctx, const void* d_poly, size_t len, int64_t* degree) {
     CHECK_CTX(ctx);
     if ((!d_poly && len) || !degree) return plonk_fail(PLONK_ERR_ARG, "plonk_poly_degree_dev: null");
@@ -1779,6 +1812,20 @@ extern "C" int plonk_g1_sum_tree_dev(plonk_ctx* ctx, const void* d_points, size_
     if (!d_tree) return plonk_fail(PLONK_ERR_ARG, "plonk_g1_sum_tree_dev: d_tree is null");
     HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
     const int rc = g1_sum_tree_run(ctx->curve, d_points, k, d_mask, d_tree, ctx->stream);
+    HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
+    ctx->ev_valid = true;
+    return rc;
+}
+// A KZG opening outside a proof -> its pair of the folded check (csrc/kzg_kernels.hpp); the fold and the pairing are the batch verifier's.
+extern "C" int plonk_kzg_pairs_dev(plonk_ctx* ctx, size_t k, const void* d_openings, const void* d_rho, const uint64_t* g_xy, void* d_out_points, void* d_status) {
+    CHECK_CTX(ctx);
+    if (k == 0) return PLONK_OK;
+    if (k > (1u << 22)) return plonk_fail(PLONK_ERR_ARG, "plonk_kzg_pairs_dev: %zu openings (at most 2^22 per call)", k);
+    if (!d_openings || !d_rho || !g_xy || !d_out_points || !d_status) return plonk_fail(PLONK_ERR_ARG, "plonk_kzg_pairs_dev: null");
+    int rc = ensure_scratch2(ctx, kzg_pairs_scratch_bytes(k));
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+    rc = kzg_pairs_run(ctx->curve, d_openings, d_rho, k, g_xy, d_out_points, d_status, ctx->d_scratch2, ctx->stream);
     HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
     ctx->ev_valid = true;
     return rc;

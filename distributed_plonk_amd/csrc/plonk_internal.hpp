@@ -244,6 +244,11 @@ int verify_batch_multi_run(int curve, const void* d_key_table, size_t n_vks, con
 // k pairs of affine points (a non-zero mask word reads as two infinities) -> the heap-ordered tree of pairwise sums, 2P - 1 pairs for P the
 // next power of two >= k: one launch for the leaves, one per level above them.  Enqueued only.
 int g1_sum_tree_run(int curve, const void* d_points, size_t k, const void* d_mask, void* d_tree, hipStream_t stream);
+// k KZG openings [C, pi, z, y] -> k pairs [rho B, rho A] and k status words (kzg_kernels.hpp, built in synth.hip).  g_xy: HOST.  scratch:
+// kzg_pairs_scratch_bytes(k).  Enqueued only.
+size_t kzg_pairs_scratch_bytes(size_t k);
+int kzg_pairs_run(int curve, const void* d_openings, const void* d_rho, size_t k, const uint64_t* g_xy, void* d_out, void* d_status, void* scratch,
+                  hipStream_t stream);
 // ark-serialize bytes <-> Montgomery limbs (codec_kernels.hpp, built in synth.hip).  Element i = o * inner + j of a launch sits at
 // base + o * stride + j * inner_stride on both sides (bytes on the byte side, u64 on the limb side) and reports into status[o * status_stride];
 // base pointers already carry the offset of element 0.  Status words are OR-ed into, never cleared, except by codec_proofs_run.  Enqueued only.
@@ -325,6 +330,13 @@ int poly_eval_run(NttTables& T, const void* d_poly, size_t len, const uint64_t* 
 int poly_lincomb_run(NttTables& T, size_t k, const void* const* polys, const size_t* lens, const uint64_t* coeffs, void* d_out, size_t out_len,
                      hipStream_t stream);
 int poly_div_linear_run(NttTables& T, const void* d_poly, size_t len, const uint64_t* point, void* d_out, void* scratch, hipStream_t stream);
+// one polynomial at m device-resident points (kzg_kernels.hpp, built in poly_ops.hip): values, quotient rows (d_quot NULL: values only) and
+// a status word per point.  scratch: poly_open_many_scratch_bytes(len, m).  Enqueued only.
+size_t poly_open_many_scratch_bytes(size_t len, size_t m);
+size_t poly_open_many_tile();
+size_t poly_open_many_top_lanes();
+int poly_open_many_run(NttTables& T, const void* d_poly, size_t len, const void* d_points, size_t m, void* d_values, void* d_quot, size_t q_stride,
+                       void* d_status, void* scratch, hipStream_t stream);
 int blind_run(NttTables& T, void* d_poly, size_t n, const uint64_t* blinders, size_t k, hipStream_t stream);
 int poly_degree_run(const void* d_poly, size_t len, int64_t* degree, void* scratch, hipStream_t stream);
 size_t coset_scratch_bytes(size_t size);

@@ -847,6 +847,12 @@ int poly_div_linear_run(NttTables& T, const void* d_poly, size_t len, const uint
     return PLONK_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- openings at many points
+// one polynomial at M device-resident points, values and quotient rows in one set of launches (plonk_poly_open_many_dev): kernels and launcher in their own header
+#define KZG_KERNELS_POLY
+#include "kzg_kernels.hpp"
+#undef KZG_KERNELS_POLY
+
 // ---------------------------------------------------------------------------------------------- arbitrary cosets
 // Evaluation of a coefficient vector on {shift * w_size^k, k < size} and its inverse, for ANY shift — the building block of
 // coset-class parallelism (rank s of G evaluates every polynomial on the points g*w_m^(s+Gk) = (g*w_m^s) * w_(m/G)^k, which

@@ -374,3 +374,7 @@ int synth_circuit_dev(int curve, uint64_t seed, size_t n, size_t num_inputs, con
 #include "verify_kernels.hpp"
 // what a prover, a ceremony and a key file hand over is bytes: ark-serialize's G1 and Fr encodings read and written on the device
 #include "codec_kernels.hpp"
+// a KZG opening outside a proof -> its pair of the folded pairing check (plonk_kzg_pairs_dev), on vfy's point loads and status bits
+#define KZG_KERNELS_POINTS
+#include "kzg_kernels.hpp"
+#undef KZG_KERNELS_POINTS

@@ -127,6 +127,7 @@ class PlonkWorker:
         self.ctx = ctx
         self._tasks = {}
         self._keepalive = []
+        self.n_bases = 0                                  # points of the resident commit key (init / init_dev / init_bytes)
 
     def close(self):
         if self.ctx:
@@ -181,6 +182,7 @@ class PlonkWorker:
         """worker.rs:126-157.  bases: (n, 2*Q) x||y Montgomery limbs, or raw ark bytes for PLONK_BASES_ARK."""
         if bases is None or len(bases) == 0:
             check(self.lib.plonk_init(self.ctx, None, 0, layout, domain_size, quot_domain_size))
+            self.n_bases = 0
             return
         if layout == _ffi.PLONK_BASES_XY:
             b = _u64(bases)
@@ -189,9 +191,11 @@ class PlonkWorker:
             b = np.ascontiguousarray(bases, dtype=np.uint8)
             n = b.size // (16 * self.q64 + 8)
         check(self.lib.plonk_init(self.ctx, _ptr(b), n, layout, domain_size, quot_domain_size))
+        self.n_bases = n
 
     def init_dev(self, d_bases_ptr: int, n_bases: int, domain_size: int, quot_domain_size: int):
         check(self.lib.plonk_init_dev(self.ctx, d_bases_ptr, n_bases, domain_size, quot_domain_size))
+        self.n_bases = n_bases
 
     # ------------------------------------------------------------------ PlonkSlave @1
     def var_msm(self, workload: MsmWorkload, scalars: np.ndarray) -> np.ndarray:
@@ -386,6 +390,12 @@ class PlonkWorker:
         """quotient of poly / (X - point), remainder dropped (dispatcher2.rs:651-666): length-1 coefficients."""
         z = _u64(point)
         check(self.lib.plonk_poly_div_linear_dev(self.ctx, d_poly, length, _ptr(z), d_out))
+
+    def poly_open_many_dev(self, d_poly: int, length: int, d_points: int, m: int, d_values: int, d_quotients: int, q_stride: int, d_status: int):
+        """d_values[j] = poly(points[j]) and row j of d_quotients (q_stride Fr apart; 0 = values only) = poly / (X - points[j]) for m points on the
+        device; d_status: m u32, 8 for a point that is no residue (plonk_poly_open_many_dev).  Enqueued on the context's stream, not synchronised."""
+        check(self.lib.plonk_poly_open_many_dev(self.ctx, d_poly or None, length, d_points or None, m, d_values or None, d_quotients or None, q_stride,
+                                                d_status or None))
 
     def coset_eval_dev(self, d_poly: int, length: int, size: int, shift, d_out: int):
         """d_out[k] = poly(shift * w_size^k), k < size (any shift; length <= 8*size folds back)."""
@@ -617,6 +627,12 @@ class PlonkWorker:
         """k pairs of affine points -> the heap-ordered tree of their pairwise sums (plonk_g1_sum_tree_dev).  Enqueued, not synchronised."""
         check(self.lib.plonk_g1_sum_tree_dev(self.ctx, d_points or None, k, d_mask or None, d_tree or None))
 
+    def kzg_pairs_dev(self, k: int, d_openings: int, d_rho: int, g_xy, d_out_points: int, d_status: int):
+        """k opening records [C, pi, z, y] -> k pairs [rho B, rho A] and k status words (plonk_kzg_pairs_dev); g_xy: the open key's G, host
+        limbs.  Enqueued, not synchronised."""
+        g = None if g_xy is None else _u64(g_xy)
+        check(self.lib.plonk_kzg_pairs_dev(self.ctx, k, d_openings or None, d_rho or None, _ptr(g), d_out_points or None, d_status or None))
+
     def codec_first_bad_dev(self, d_status: int, count: int, status_stride: int = 1) -> int:
         """The lowest index with a non-zero status word, -1 when there is none (plonk_codec_first_bad_dev).  Synchronises."""
         first = C.c_int64(-1)
@@ -631,7 +647,9 @@ class PlonkWorker:
         enc = codec.ENCODINGS[encoding]
         if b.size != n_bases * codec.g1_nbytes(self.curve_name, encoding):
             raise ValueError(f"init_bytes: {b.size} bytes for {n_bases} {encoding} points")
+        self.n_bases = 0                                  # a bad point leaves the worker without bases
         check(self.lib.plonk_init_bytes(self.ctx, _ptr(b) if n_bases else None, n_bases, enc, 1 if check_subgroup else 0, domain_size, quot_domain_size))
+        self.n_bases = n_bases
 
     def circuit_scatter_inputs_dev(self, d_input_vars: int, num_inputs: int, d_inputs: int, d_witness: int, num_vars: int):
         """witness[input_vars[k]] = inputs[k] on the device (plonk_circuit_scatter_inputs_dev); d_input_vars: u32.  Synchronises."""

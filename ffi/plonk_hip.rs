@@ -136,6 +136,10 @@ extern "C" {
     pub fn plonk_poly_eval_dev(ctx: *mut plonk_ctx, d_poly: *const c_void, len: usize, point: *const u64, out: *mut u64) -> c_int;
     pub fn plonk_poly_lincomb_dev(ctx: *mut plonk_ctx, k: usize, d_polys: *const *const c_void, lens: *const usize, coeffs: *const u64, d_out: *mut c_void, out_len: usize) -> c_int;
     pub fn plonk_poly_div_linear_dev(ctx: *mut plonk_ctx, d_poly: *const c_void, len: usize, point: *const u64, d_out: *mut c_void) -> c_int;
+    pub fn plonk_poly_open_many_dev(ctx: *mut plonk_ctx, d_poly: *const c_void, len: usize, d_points: *const c_void, m: usize,
+                                    d_values: *mut c_void, d_quotients: *mut c_void, q_stride: usize, d_status: *mut c_void) -> c_int;
+    pub fn plonk_poly_open_many_tile() -> usize;
+    pub fn plonk_poly_open_many_top_lanes() -> usize;
     pub fn plonk_poly_degree_dev(ctx: *mut plonk_ctx, d_poly: *const c_void, len: usize, degree: *mut i64) -> c_int;
     pub fn plonk_blind_dev(ctx: *mut plonk_ctx, d_poly: *mut c_void, n: usize, blinders: *const u64, k: usize) -> c_int;
     pub fn plonk_coset_eval_dev(ctx: *mut plonk_ctx, d_poly: *const c_void, len: usize, size: usize, shift: *const u64, d_out: *mut c_void) -> c_int;
@@ -195,6 +199,7 @@ extern "C" {
                                         d_pub_inputs: *const c_void, d_pub_offsets: *const c_void, pub_total: usize, d_rho: *const c_void, d_out_points: *mut c_void,
                                         d_status: *mut c_void, d_debug: *mut c_void) -> c_int;
     pub fn plonk_g1_sum_tree_dev(ctx: *mut plonk_ctx, d_points: *const c_void, k: usize, d_mask: *const c_void, d_tree: *mut c_void) -> c_int;
+    pub fn plonk_kzg_pairs_dev(ctx: *mut plonk_ctx, k: usize, d_openings: *const c_void, d_rho: *const c_void, g_xy: *const u64, d_out_points: *mut c_void, d_status: *mut c_void) -> c_int;
     pub fn plonk_g1_from_bytes_dev(ctx: *mut plonk_ctx, d_bytes: *const c_void, in_stride: usize, count: usize, encoding: c_int, check_subgroup: c_int, d_out_xy: *mut c_void, out_stride_u64: usize, d_status: *mut c_void, status_stride: usize) -> c_int;
     pub fn plonk_g1_to_bytes_dev(ctx: *mut plonk_ctx, d_xy: *const c_void, in_stride_u64: usize, count: usize, encoding: c_int, d_bytes: *mut c_void, out_stride: usize) -> c_int;
     pub fn plonk_fr_from_bytes_dev(ctx: *mut plonk_ctx, d_bytes: *const c_void, in_stride: usize, count: usize, d_out: *mut c_void, out_stride_u64: usize, d_status: *mut c_void, status_stride: usize) -> c_int;

@@ -252,6 +252,17 @@ int plonk_poly_lincomb_dev(plonk_ctx* ctx, size_t k, const void* const* d_polys,
                            void* d_out, size_t out_len);
 /* d_out[0..len-1) = quotient of poly / (X - point), remainder dropped: the synthetic-division loops of :651-666,672-688. */
 int plonk_poly_div_linear_dev(plonk_ctx* ctx, const void* d_poly, size_t len, const uint64_t* point, void* d_out);
+/* y_j = f(z_j) and q_j = (f - y_j)/(X - z_j) for m device-resident points, one set of launches.
+ * d_values: m Fr.  d_quotients: NULL (values only) or m rows of q_stride Fr (q_stride >= len - 1), row j = q_j.
+ * d_status: m u32, 0 ok, | 8 point not canonical.  len < 2^30, m <= 2^16.  Enqueued on the context's stream, not synchronised.
+ * Points, coefficients and results are Montgomery Fr.  A point >= the modulus gets the value 0 and a row of zeros; the words of a row beyond
+ * len - 1 are left alone.  len == 0: every value 0; len == 1: the values f_0, nothing written to d_quotients; m == 0: no launch.  An output
+ * that overlaps d_poly (or d_points) is PLONK_ERR_ARG.  No point is special: 0 is opened by the same launches as any other (csrc/kzg_kernels.hpp). */
+int plonk_poly_open_many_dev(plonk_ctx* ctx, const void* d_poly, size_t len, const void* d_points, size_t m,
+                             void* d_values, void* d_quotients, size_t q_stride, void* d_status);
+/* The shape of plonk_poly_open_many_dev's kernels: coefficients per tile, lanes of the per-point top scan (tests follow them). */
+size_t plonk_poly_open_many_tile(void);
+size_t plonk_poly_open_many_top_lanes(void);
 /* *degree = index of the highest non-zero coefficient, -1 for the zero polynomial: DensePolynomial::degree() after the
  * trimming of from_coefficients_vec — the WrongQuotientPolyDegree check of :511-518 without a host copy.  Synchronises. */
 int plonk_poly_degree_dev(plonk_ctx* ctx, const void* d_poly, size_t len, int64_t* degree);
@@ -545,6 +556,12 @@ int plonk_verify_batch_multi_dev(plonk_ctx* ctx, const plonk_verify_key* vks, si
  * is complete (equal inputs, opposite inputs — the sum is written (0, 0) —, infinity on either side or both).  One launch for the leaves
  * and one per level, one lane per output point, one inversion per inner point; enqueued on the context's stream; k = 0 is a no-op. */
 int plonk_g1_sum_tree_dev(plonk_ctx* ctx, const void* d_points, size_t k, const void* d_mask, void* d_tree);
+/* k opening records [C (2Q u64), pi (2Q u64), z (4 u64), y (4 u64)] -> d_out_points k x [rho B, rho A] as plonk_verify_batch_dev writes them,
+ * d_status k u32: | 1 off the curve, | 2 outside the r-subgroup (BLS12-381), | 8 coordinate or scalar not canonical; a record with a status gets
+ * (0, 0) twice.  g_xy: the open key's G (HOST, 2Q u64).  Feeds plonk_g1_sum_tree_dev unchanged.  Enqueued, not synchronised; needs no SRS.
+ * An opening (C, pi, z, y) of a KZG commitment holds iff e(pi, [tau]_2) = e(C - y G + z pi, [1]_2); with d_rho (k Fr) the pair is
+ * A = rho pi, B = rho C + (rho z) pi - (rho y) G.  Points affine Montgomery with (0, 0) = infinity, z, y and rho Montgomery Fr; k <= 2^22. */
+int plonk_kzg_pairs_dev(plonk_ctx* ctx, size_t k, const void* d_openings, const void* d_rho, const uint64_t* g_xy, void* d_out_points, void* d_status);
 /* ark-serialize 0.3 bytes <-> Montgomery limbs (`to_bytes!` of the reference; csrc/codec_kernels.hpp), one lane per element.
  * A G1Affine is, compressed, its x coordinate little-endian (32 B BN254 / 48 B BLS12-381) with two flags in the top bits of the last byte:
  * 0x80 "y is the larger of {y, -y} as integers", 0x40 infinity; uncompressed, x then y (64 B / 96 B), the last byte of y carrying only 0x40.
